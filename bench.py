@@ -44,6 +44,32 @@ FWD_GFLOP_PER_CLIP = 325.56            # SURVEY.md §6 (conv + addmm + bmm, forw
 TRAIN_GFLOP_PER_CLIP = 993.45          # SURVEY.md §6 (fwd + bwd, positive step)
 
 
+DUMP_LIMIT_BYTES = 64 << 20            # --dump-outputs: all files together
+
+
+def detection_rows(dets):
+    """The per-clip output dictionaries of a detect step ({'1'..'nc': {'bbox_coord': [n,4], 'scores': [1,n]}}) -> float64
+    rows (clip, class, x1, y1, x2, y2, score), in the order the dictionaries hold them."""
+    rows = [[b, int(k), *bb.tolist(), float(sc)]
+            for b, d in enumerate(dets) for k, v in d.items() if len(v['bbox_coord'])
+            for bb, sc in zip(v['bbox_coord'], v['scores'].reshape(-1))]
+    return np.array(rows, dtype=np.float64).reshape(-1, 7)
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """{name: float32 / float64 array} -> path/<name>.npy.  When the arrays exceed `limit` bytes in all, each keeps a fixed,
+    seeded sample of its rows (sorted), in proportion, so that the files fit."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError(f'--dump-outputs: {name} is {v.dtype}, not float32 / float64')
+        if total > limit and v.ndim and len(v) > 1:
+            keep = len(v) * limit // total
+            v = v[np.sort(np.random.default_rng(0).choice(len(v), keep, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), v)
+
+
 def conv_algorithmic_bytes(B, H, W, Cin, N, k, stride, groups, kind):
     """ALGORITHMIC HBM bytes of one implicit-GEMM launch (every operand once): forward / data gradient = activation in +
     weights + activation out; weight gradient = both activations + the weight-sized result.  Epilogue operands that depend on the call
@@ -417,7 +443,14 @@ def parse_args(argv=None):
                     help='skip the extra detect leg with the deep-K GEMMs on the bf16 matrix pipe (split fp32 operands, opt-in mode)')
     ap.add_argument('--bulk-files', type=int, default=16384,
                     help='bulk_inference leg (configs[4] on this rank\'s shard): wav files on tmpfs -> txt files; 0 = skip')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step -- the detections of every clip, '
+                         'rows (clip, class, x1, y1, x2, y2, score) -- as DIR/detections.npy (float64; rank r > 0 of a multi-GPU run: '
+                         'detections_rank<r>.npy).  The inputs are seeded: the same arguments give the same inputs on every run')
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
 
 
 def free_port():
@@ -656,6 +689,7 @@ def main(argv=None):
     n_det += sum(len(v['bbox_coord']) for d in out for v in d.values())
     sync_all()
     dt = time.perf_counter() - t0
+    timed_out = out                                            # what the timed path returned in its last step (--dump-outputs)
     gc.enable()
     prof, ops.PROFILE = ops.PROFILE, None
     ops.PROFILE_ONLY = None
@@ -689,8 +723,9 @@ def main(argv=None):
     def replay_leg(gd, expect=None):
         """Timed replays of the captured step: `gd.lanes` batches per replay, in flight on the GPU together; EXACTLY K steps = K // lanes
         replays + (K mod lanes) eager steps behind them (in a lane of their own: the graph's branches own lanes 0 .. lanes-1).
-        -> seconds, or None.  Every rank passes BOTH barriers whatever happens to it in between (a rank-local exception used to leave
-        that rank two barriers short and its peers waiting for the collective timeout)."""
+        -> (seconds, or None; the per-clip outputs of the last step).  Every rank passes BOTH barriers whatever happens to it in
+        between (a rank-local exception used to leave that rank two barriers short and its peers waiting for the collective timeout,
+        ADVICE r3)."""
         nonlocal graph_note
         L = gd.lanes
         n_rep, n_tail = a.steps // L, a.steps % L
@@ -719,7 +754,7 @@ def main(argv=None):
             pending[1].synchronize()
             return [fast_rcnn.dets_to_dicts(h[0], h[1], model.args.num_classes) for h in pending[0]]
 
-        ok, dt_leg = True, None
+        ok, dt_leg, last = True, None, None
         try:
             for _ in range(max(1, -(-a.warmup // L))):
                 finish_g(launch_g())
@@ -739,12 +774,14 @@ def main(argv=None):
                             n_det_g += sum(len(v['bbox_coord']) for out in finish_g(pend) for d in out for v in d.values())
                         pend = cur
                     if pend is not None:
-                        n_det_g += sum(len(v['bbox_coord']) for out in finish_g(pend) for d in out for v in d.values())
+                        outs = finish_g(pend)
+                        n_det_g += sum(len(v['bbox_coord']) for out in outs for d in out for v in d.values())
+                        last = outs[-1]
                     for _ in range(n_tail):                    # K is not a multiple of the lanes: the remaining steps, eagerly
                         torch.cuda.current_stream().wait_stream(gd.stream)
                         with ops.lane(max(gd.lane_ids) + 1):
-                            out = step()
-                        n_det_g += sum(len(v['bbox_coord']) for d in out for v in d.values())
+                            last = step()
+                        n_det_g += sum(len(v['bbox_coord']) for d in last for v in d.values())
                     want = n_det if expect is None else expect
                     if n_det_g != want:
                         raise RuntimeError(f'the replayed steps returned {n_det_g} detections, the eager ones {want}')
@@ -760,15 +797,17 @@ def main(argv=None):
             if dt_leg is not None:
                 graph_note = 'hipGraph replay failed on another rank; value is the eager loop'
             dt_leg = None
-        return dt_leg
+        return dt_leg, last
 
     # the one-lane graph is measured and released before the multi-lane one exists (memory: every live detector owns its lanes' scratch)
     dt_g = dt_g1 = dt_g2 = None
     lanes_used = 0
     gd = capture(1)
     if gd is not None:
-        dt_g1 = replay_leg(gd)
+        dt_g1, out_g1 = replay_leg(gd)
         dt_g, lanes_used = dt_g1, (1 if dt_g1 is not None else 0)
+        if dt_g1 is not None:
+            timed_out = out_g1
     gd = None
     gc.collect()
     torch.cuda.empty_cache()
@@ -776,9 +815,9 @@ def main(argv=None):
         note1 = graph_note
         gd = capture(n_lanes)
         if gd is not None:
-            dt_g2 = replay_leg(gd)                              # `n_lanes` batches in flight together: the headline when it is the faster loop
+            dt_g2, out_g2 = replay_leg(gd)                              # `n_lanes` batches in flight together: the headline when it is the faster loop
             if dt_g2 is not None and dt_g2 < dt_g1:
-                dt_g, lanes_used = dt_g2, n_lanes
+                dt_g, lanes_used, timed_out = dt_g2, n_lanes, out_g2
         if dt_g2 is None and dt_g1 is not None:                 # the one-lane figure stands; keep the reason the multi-lane leg gave up
             graph_note = None if graph_note is None else 'multi-lane leg: ' + graph_note
         gd = None
@@ -788,6 +827,9 @@ def main(argv=None):
     multi_lane = None if dt_g2 is None else {'lanes': n_lanes, 'ms_per_step': dt_g2 / a.steps * 1e3, 'clips_per_s_per_gpu': B * a.steps / dt_g2}
     if dt_g is not None:
         dt = dt_g
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {'detections' + (f'_rank{rank}' if rank else ''): detection_rows(timed_out)})
+
     def gemm_gflop(tag):
         Cin, N, k, H, W, Bn, groups, stride = tag[:8]
         if len(tag) == 9 and isinstance(tag[8], tuple) and tag[8][0] == 'rpn-composite':      # k taps x 1, one output row: W cells
@@ -826,7 +868,7 @@ def main(argv=None):
             prof_s, ops.PROFILE, ops.PROFILE_ONLY = ops.PROFILE, None, None
             note0 = graph_note
             gd = capture(max(1, lanes_used))
-            dt_s = replay_leg(gd, expect=n_det_split) if gd is not None else None
+            dt_s = replay_leg(gd, expect=n_det_split)[0] if gd is not None else None
             gd = None
             gc.collect()
             torch.cuda.empty_cache()

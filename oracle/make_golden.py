@@ -444,10 +444,65 @@ def frontend_golden():
     np.savez_compressed(os.path.join(OUT, 'frontend.npz'), **g)
 
 
+LIVE_PIXEL_CASES = ('chunkq', 'labels', 'short')
+
+
+def image_digest(im):
+    """SHA-256 of a float32 spectrogram window (-0.0 folded into +0.0): equal digests = the same pixels, bit for bit."""
+    import hashlib
+    return np.frombuffer(hashlib.sha256((np.asarray(im, dtype=np.float32) + np.float32(0)).tobytes()).digest(), dtype=np.uint8)
+
+
+def reference_checks_golden():
+    """What tests/test_oracle_vs_reference.py and the every-pixel front-end test compare the oracle with ->
+    tests/golden/reference_checks.npz: the eval forward at another filler seed / input, the anchors and shifts, the
+    exception the reference raises with `--position_embedding learned`, and a digest of every window of three
+    front-end cases (all pixels, bit for bit, without storing the images)."""
+    import tempfile
+    from . import nets_ref as O
+    g = {}
+    args = ref_import.default_args()
+    assert vars(O.make_cfg(args)) == vars(O.make_cfg())
+    model, _ = ref_import.build_reference_model(args)
+    sd = synth.fill_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}, seed=5)
+    model.load_state_dict(sd)
+    model.eval()
+    x = torch.from_numpy(synth.image_batch(7, 1))[:, None]
+    with torch.no_grad():
+        o = model.forward_first_stage(x)
+        for i, f in enumerate(o['fpn_out']):
+            pack(g, f'seed5.fpn{i}', f)
+        pack(g, 'seed5.rois', o['rois'])
+        pack_dets(g, 'seed5.dets_min0.05', model(x, min_score=0.05))
+    from nbm_model.nets.util.nets_utils import generate_anchors_frcnn, get_anchor_shifts_frcnn
+    g['anchors.base'] = np.asarray(generate_anchors_frcnn(16, [0.5, 1, 2], 2 ** np.arange(5)))
+    g['anchors.shifts'] = np.asarray(get_anchor_shifts_frcnn(64, 24, 16))
+    m, _ = ref_import.build_reference_model(ref_import.default_args(position_embedding='learned'))
+    try:
+        with torch.no_grad():
+            m.forward_first_stage(torch.zeros(1, 1, 375, 1024))
+        g['learned_pe.error'] = np.array('')
+    except Exception as exc:
+        g['learned_pe.error'] = np.array(type(exc).__name__)
+    PD = install_frontend_stubs()
+    with tempfile.TemporaryDirectory() as d:
+        for case in FRONTEND_CASES:
+            if case[0] not in LIVE_PIXEL_CASES:
+                continue
+            _, imgs, _ = run_reference_frontend(PD, *case, d)
+            g[f'frontend.{case[0]}.shape'] = np.array([np.shape(im) for im in imgs], dtype=np.int64)
+            g[f'frontend.{case[0]}.sha256'] = np.stack([image_digest(im) for im in imgs])
+    np.savez_compressed(os.path.join(OUT, 'reference_checks.npz'), **g)
+    print('reference_checks: %d arrays, %d detections@0.05, learned PE: %s' % (len(g), len(g['seed5.dets_min0.05']),
+                                                                                g['learned_pe.error']))
+
+
 def main():
     warnings.filterwarnings('ignore')
     torch.manual_seed(0)
     os.makedirs(OUT, exist_ok=True)
+    if '--reference-checks-only' in sys.argv:
+        return reference_checks_golden()
     if '--tf-only' in sys.argv:
         return tf_rcnn_golden()
     if '--variants-only' in sys.argv:
@@ -472,6 +527,7 @@ def main():
     metrics_golden()
     labels_golden()
     frontend_golden()
+    reference_checks_golden()
     args = ref_import.default_args()
     model, crit = ref_import.build_reference_model(args, train=False)
     shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}

@@ -4,11 +4,11 @@ This is the *oracle* for the detector half of the hot path (SURVEY.md §8a rows
 M1..M10, P1..P5, L1..L5).  It is a functional re-expression of the reference's
 algorithm -- every function cites the reference file:line it follows -- written
 batched and loop-free where the reference loops in Python.  It is pinned by
-(a) `tests/test_oracle_vs_reference.py`, which runs the real reference (imported
-with `oracle/tv_standin.py`) beside it in the build container, and (b) the
-golden fixtures in `tests/golden/` generated by `oracle/make_golden.py` from the
-real reference.  Only tests, `__graft_entry__.smoke()` and `bench.py`'s
-`cpu_baseline` leg may import it; the product path never does.
+the golden fixtures in `tests/golden/` that `oracle/make_golden.py` generates
+from the real reference (imported with `oracle/tv_standin.py`), among them
+`reference_checks.npz` for `tests/test_oracle_vs_reference.py`.  Only tests,
+`__graft_entry__.smoke()` and `bench.py`'s `cpu_baseline` leg may import it;
+the product path never does.
 
 All tensors are NCHW like the reference.  Weights come in as a plain
 `state_dict` (SURVEY.md Appendix B names).

@@ -1,8 +1,7 @@
 """TEST INFRASTRUCTURE ONLY — import the reference's `nbm_model.nets` in THIS container.
 
-Used by `oracle/make_golden.py` and by the container-only tests that validate the
-oracle restatement against the real reference (they skip when /root/reference is
-absent, which is always the case on the GPU box).  Never imported by the product.
+Used by `oracle/make_golden.py` only: the tests compare with what it stored under
+tests/golden/, never with the reference itself.  Never imported by the product.
 
 * torchvision is provided by `oracle/tv_standin.py`.
 * `train.py` cannot be imported (tensorboard + script-relative imports), so the
