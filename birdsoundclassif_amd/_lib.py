@@ -93,6 +93,11 @@ SIGNATURES = {
     'nbm_nms_batched': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _P],
     'nbm_roi_pool': [C.POINTER(RoiDesc), _P],
     'nbm_rcnn_post': [_P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _I, _P],
+    # ---- per-file merge (run_detection.merge_images)
+    'nbm_merge_collect': [_P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P],
+    'nbm_merge_nms_workspace': [_I, C.POINTER(C.c_int64)],
+    'nbm_merge_nms': [_P, _P, _I, _F, _P, _L, _P, _P, _P],
+    'nbm_merge_gather': [_P, _P, _P, _P, _P, _I, _P, _P, _P],
     # ---- training path
     'nbm_conv_dgrad': [C.POINTER(BwdDesc), _P],
     'nbm_conv_wgrad': [C.POINTER(BwdDesc), _P],

@@ -749,6 +749,69 @@ def rcnn_post(rois, n_roi, bbox_reg, bbox_cls, img_w, img_h, nms_thresh, min_sco
     return det, n_det
 
 
+# --------------------------------------------------------------------------- per-file merge (run_detection.merge_images)
+MERGE_MAX_N = 131072          # NBM_MERGE_MAX_N
+
+
+def merge_collect(det, n_det, w_pix, hop, spectrogram_length, num_classes):
+    """det [n_img,cap,6] (rcnn_post rows of the file's windows in order), n_det int32 [n_img] -> boxes [n_img*cap,4] (shifted),
+    scores [n_img*cap], species int32 [n_img*cap], n int32 [1]: the first n rows in the reference's collected order."""
+    _chk(det, name='det'), _chk(n_det, torch.int32, 'n_det')
+    n_img, cap = det.shape[:2]
+    dev = det.device
+    cells = torch.empty((n_img * num_classes,), device=dev, dtype=torch.int32)
+    boxes = torch.empty((n_img * cap, 4), device=dev, dtype=torch.float32)
+    scores = torch.empty((n_img * cap,), device=dev, dtype=torch.float32)
+    species = torch.empty((n_img * cap,), device=dev, dtype=torch.int32)
+    n = torch.empty((1,), device=dev, dtype=torch.int32)
+    check(lib().nbm_merge_collect(_ptr(det), _ptr(n_det), n_img, cap, int(num_classes), int(w_pix), int(hop),
+                                  int(spectrogram_length), _ptr(cells), _ptr(boxes), _ptr(scores), _ptr(species), _ptr(n),
+                                  _stream()), 'nbm_merge_collect')
+    return boxes, scores, species, n
+
+
+def merge_nms_workspace_bytes(cap):
+    if not 0 <= cap <= MERGE_MAX_N:
+        raise ValueError(f'merge NMS: {cap} boxes is above the limit of {MERGE_MAX_N}')
+    nbytes = C.c_int64()
+    check(lib().nbm_merge_nms_workspace(int(cap), C.byref(nbytes)), 'nbm_merge_nms_workspace')
+    return nbytes.value
+
+
+def merge_nms(boxes, n, thresh, cap=None):
+    """Greedy NMS in the given order over the first n (device int32 [1]) of boxes [>=cap,4]; cap (default len(boxes)) <=
+    MERGE_MAX_N -> keep int32 [cap] (first n_keep valid), n_keep int32 [1]."""
+    _chk(boxes, name='boxes'), _chk(n, torch.int32, 'n')
+    cap = boxes.shape[0] if cap is None else int(cap)
+    if cap > boxes.shape[0]:
+        raise ValueError('merge NMS: cap exceeds the box buffer')
+    ws_bytes = merge_nms_workspace_bytes(cap)
+    ws = torch.empty((ws_bytes,), device=boxes.device, dtype=torch.uint8)
+    keep = torch.empty((max(cap, 1),), device=boxes.device, dtype=torch.int32)
+    n_keep = torch.empty((1,), device=boxes.device, dtype=torch.int32)
+    check(lib().nbm_merge_nms(_ptr(boxes), _ptr(n), cap, float(thresh), _ptr(ws), ws_bytes, _ptr(keep), _ptr(n_keep),
+                              _stream()), 'nbm_merge_nms')
+    return keep, n_keep
+
+
+def merge_gather(boxes, scores, species, keep, n_keep, cap):
+    """-> one float32 tensor [1 + 6*cap]: word 0 holds the row count (int32 bits), then rows {species,x1,y1,x2,y2,score} in the
+    kept order -- a single device-to-host copy brings back the whole merge."""
+    _chk(boxes, name='boxes'), _chk(scores, name='scores'), _chk(species, torch.int32, 'species')
+    _chk(keep, torch.int32, 'keep'), _chk(n_keep, torch.int32, 'n_keep')
+    out = torch.empty((1 + 6 * cap,), device=boxes.device, dtype=torch.float32)
+    check(lib().nbm_merge_gather(_ptr(boxes), _ptr(scores), _ptr(species), _ptr(keep), _ptr(n_keep), int(cap), _ptr(out[1:]),
+                                 _ptr(out[:1].view(torch.int32)), _stream()), 'nbm_merge_gather')
+    return out
+
+
+def unpack_merged(out):
+    """Host side of merge_gather's buffer -> float32 rows [n,6]."""
+    out = out.cpu() if out.is_cuda else out
+    n = int(out[:1].view(torch.int32)[0])
+    return out[1:1 + 6 * n].view(n, 6)
+
+
 # =========================================================================== training path
 from ._lib import BwdDesc  # noqa: E402
 

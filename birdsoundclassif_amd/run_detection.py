@@ -1,7 +1,9 @@
 """Per-file detection driver (reference nbm_model/run_detection.py): `load_model`, `run_detection`, `merge_images`.
 
 `run_detection` keeps the reference's signature and output dict; the spectrogram windows stay on the GPU between the
-front end and the detector, and the cross-window merge runs the device NMS."""
+front end and the detector, and the whole cross-window merge of the file runs on the device (csrc/merge.hip): collect,
+greedy NMS and gather, then one device-to-host copy.  `merge_images` is the reference-named dictionary API; its NMS runs
+on the same device entry point.  Both take up to ops.MERGE_MAX_N = 131 072 candidate boxes per file."""
 import json
 import os
 
@@ -56,17 +58,11 @@ def merge_images(fp, outputs, num_classes, nms_thresh=0.3):
         return class_bbox
     boxes, scores, species = torch.cat(boxes), torch.cat(scores), np.array(species)
     n = len(boxes)
-    cap = max(64, (n + 63) // 64 * 64)
-    if cap > 4096:
-        raise NotImplementedError('more than 4096 candidate boxes in one file')
-    bx = torch.zeros((1, cap, 4), device=device)
-    sx = torch.zeros((1, cap), device=device)
-    bx[0, :n], sx[0, :n] = boxes.to(device), scores.to(device)
-    # index payload rides in the score slot so that the kept order can be recovered exactly
-    idx_payload = torch.arange(cap, device=device, dtype=torch.float32)[None]
+    if n > ops.MERGE_MAX_N:
+        raise ValueError(f'{n} candidate boxes in one file: the device merge handles up to {ops.MERGE_MAX_N}')
     n_in = torch.full((1,), n, device=device, dtype=torch.int32)
-    _, kept_idx, n_out = ops.nms_batched(bx, idx_payload.contiguous(), n_in, nms_thresh, cap)
-    keep = kept_idx[0, :int(n_out.item())].long().cpu()
+    kept_idx, n_out = ops.merge_nms(boxes.to(device).contiguous(), n_in, nms_thresh)
+    keep = kept_idx[:int(n_out.item())].long().cpu()
     boxes, scores, species = boxes[keep], scores[keep], species[keep.numpy()]
     for j in range(1, num_classes + 1):
         m = torch.from_numpy(species == j)
@@ -89,17 +85,47 @@ def run_detection(model, config, wav_path, bird_dicts_path, min_score=0.5, bs=10
         raise NotImplementedError('recordings longer than 1.5e8 samples come back as nested per-split image lists, which '
                                   'the reference detection loop cannot consume either; split the recording first')
     imgs = fp.images_device                                   # [n_img, 375, 1024] on the GPU
-    outputs = []
-    for s in range(0, imgs.shape[0], bs):
-        with torch.no_grad():
-            outputs.append(model(imgs[s:s + bs][:, None].contiguous(), min_score=min_score))
+    n_img = imgs.shape[0]
+    if n_img == 0:
+        return {}
+    det_all, n_all = None, None
+    for s in range(0, n_img, bs):
+        # the same model calls (and batch coupling of the proposal counts) as `model(...)` per group of bs windows; the rows
+        # live in reused scratch, so they are copied out before the next call
+        det, n_det = model.detect(imgs[s:s + bs][:, None].contiguous(), 0.3, min_score)
+        if det_all is None:
+            det_all = torch.empty((n_img,) + tuple(det.shape[1:]), device=det.device, dtype=det.dtype)
+            n_all = torch.empty((n_img,), device=det.device, dtype=torch.int32)
+        det_all[s:s + det.shape[0]].copy_(det)
+        n_all[s:s + det.shape[0]].copy_(n_det)
     with open(bird_dicts_path, 'r') as f:
         birds_dict = json.load(f)
     birds_dict.update({'Non bird sound': 0})
     reverse_dict = {idx: name for name, idx in birds_dict.items()}
-    class_bbox = merge_images(fp, outputs, config.num_classes)
-    return {reverse_dict[idx]: {k: v.cpu().numpy().tolist() for k, v in class_bbox[str(idx)].items()}
-            for idx in range(1, len(class_bbox) + 1) if len(class_bbox[str(idx)]['bbox_coord']) > 0}
+    rows = merge_device(fp, det_all, n_all, config.num_classes)
+    species = rows[:, 0].to(torch.int64).numpy()
+    out = {}
+    for idx in range(1, config.num_classes + 1):
+        m = species == idx
+        if m.any():
+            sel = rows[torch.from_numpy(m)]
+            out[reverse_dict[idx]] = {'bbox_coord': sel[:, 1:5].numpy().tolist(), 'scores': sel[:, 5].numpy().tolist()}
+    return out
+
+
+def merge_device(fp, det, n_det, num_classes, nms_thresh=0.3):
+    """`merge_images` on the detector's device rows of one file: det [n_img,cap,6] ({class,x1,y1,x2,y2,score}, sorted by
+    (class, score desc) per window), n_det int32 [n_img] -> float32 CPU rows [n,6] {species,x1,y1,x2,y2,score} in the kept
+    (class-major) order.  Collect, NMS and gather are queued without a host sync; one copy brings the result back."""
+    boxes, scores, species, n = ops.merge_collect(det, n_det, fp.W_PIX, fp.HOP_SPECTRO, fp.spectrogram_length, num_classes)
+    cap = boxes.shape[0]
+    if cap > ops.MERGE_MAX_N:
+        # only reachable past ~2 600 windows, longer than the 1.5e8-sample split limit: the count decides
+        if int(n.item()) > ops.MERGE_MAX_N:
+            raise ValueError(f'{int(n.item())} candidate boxes in one file: the device merge handles up to {ops.MERGE_MAX_N}')
+        cap = ops.MERGE_MAX_N
+    keep, n_keep = ops.merge_nms(boxes, n, nms_thresh, cap)
+    return ops.unpack_merged(ops.merge_gather(boxes, scores, species, keep, n_keep, cap))
 
 
 def load_model(mod_p):

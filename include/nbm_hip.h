@@ -418,6 +418,39 @@ int nbm_rcnn_post(const float* rois, const int* n_roi, int B, int roi_cap, const
                   float nms_thresh, float min_score, int proposal_number, float* det, int* n_det,
                   int per_image /* n_roi[b] */, void* stream);
 
+/* Per-file merge of the window outputs of one recording (run_detection.py:163-249), for any box count up to
+ * NBM_MERGE_MAX_N.  nbm_merge_collect -> nbm_merge_nms -> nbm_merge_gather, all on one stream, no host sync. */
+#define NBM_MERGE_MAX_N 131072
+
+/* Collect (run_detection.py:180-221): det[n_img][cap][6] = the rows nbm_rcnn_post writes for the file's windows in order
+ * ({class, x1, y1, x2, y2, score}, sorted by (class, score desc)), n_det[n_img].  Per row of window i: the border rules as the
+ * reference's if/elif chain (:195-200; first window: x2 >= w_pix - 5, last: x1 <= 4, inner: either; each only for widths
+ * x2 - x1 < float32(0.9 * (w_pix - hop))), then x1, x2 += hop * i (one fp32 add each, :208-209), then the drop of
+ * x2 >= spectrogram_length (:211-217).  Output compacted in the reference's collected order -- class 1..num_classes, then window,
+ * then row: boxes[N][4] (shifted), scores[N], species[N] (int class), n_out[0] = N <= n_img * cap.  Rows whose class is not
+ * in 1..num_classes are dropped.  cell_ws: n_img * num_classes int32.  n_img * cap and n_img * num_classes <= 2^30. */
+int nbm_merge_collect(const float* det, const int* n_det, int n_img, int cap, int num_classes, int w_pix, int hop,
+                      int64_t spectrogram_length, int* cell_ws, float* boxes, float* scores, int* species, int* n_out,
+                      void* stream);
+
+/* Workspace bytes of nbm_merge_nms for capacity cap (0 <= cap <= NBM_MERGE_MAX_N, else NBM_EINVAL): the bitmask tiles of
+ * the dense worst case, 64 x 64 bits per pair of 64-box blocks (rb <= cb), = 512 * nb * (nb + 1) / 2 bytes with
+ * nb = ceil(cap / 64) (about cap^2 / 16: 300 MB at 69 250 boxes, 1.07 GB at 2^17), plus the block x-ranges. */
+int nbm_merge_nms_workspace(int cap, int64_t* bytes);
+
+/* Greedy NMS of nets_utils.nms with post_nms_topN = n (nets_utils.py:210-245, run_detection.py:233) over
+ * n = min(max(n_in[0], 0), cap) boxes[n][4]: walk in the GIVEN order (no re-sort), a kept box removes every later box with
+ * IoU >= thresh (fp32, +1 pixel, union = (aa + ab) - inter, no contraction).  keep[0 .. n_keep[0]) = kept indices in walk
+ * order.  Tiles of block pairs whose x-ranges cannot overlap under the +1 convention are skipped when thresh > 0.
+ * ws: ws_bytes >= nbm_merge_nms_workspace(cap).  cap <= NBM_MERGE_MAX_N and a non-null ws, else NBM_EINVAL. */
+int nbm_merge_nms(const float* boxes, const int* n_in, int cap, float thresh, void* ws, int64_t ws_bytes, int* keep,
+                  int* n_keep, void* stream);
+
+/* Gather (run_detection.py:234-249): rows[r] = {species, x1, y1, x2, y2, score} of box keep[r] for r < n_rows[0] =
+ * min(n_keep[0], cap); the kept (class-major) order, ready for one device-to-host copy. */
+int nbm_merge_gather(const float* boxes, const float* scores, const int* species, const int* keep, const int* n_keep, int cap,
+                     float* rows, int* n_rows, void* stream);
+
 /* Training, AnchorTargetLayer (layers.py:150-179, nets_utils.py:103-126): IoU (inclusive-pixel convention, the reference's fp32
  * operations in its order) of every anchor inside the image with the n_gt[b] boxes of gt[b]; amx[b][a] = index of the FIRST best box,
  * lab[b][a] = the anchor's label BEFORE the random subsampling (0: best overlap < neg_t; 1: best overlap >= pos_t, or the anchor is a
