@@ -74,6 +74,7 @@ SIGNATURES = {
     'nbm_minmax_init': [_P, _I, _P],
     'nbm_stft_db': [_P, _L, _I, _I, _I, _I, _P, _I, _I, _I, _F, _P, _L, _I, _P, _P],
     'nbm_spec_windows': [_P, _L, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P],
+    'nbm_spec_windows_table': [_P, _I, _I, _P, _I, _I, _P],
     'nbm_init_conv': [_P, _L, _P, _P, _I, _P, _P],
     'nbm_stem7x7': [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     'nbm_stem7x7_wgrad': [_P, _P, _I, _I, _I, _P, _P, _P],
@@ -91,6 +92,8 @@ SIGNATURES = {
     'nbm_rpn_decode': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     'nbm_rpn_select': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     'nbm_nms_batched': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _P],
+    'nbm_rpn_select_seg': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'nbm_nms_batched_seg': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     'nbm_roi_pool': [C.POINTER(RoiDesc), _P],
     'nbm_rcnn_post': [_P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _I, _P],
     # ---- per-file merge (run_detection.merge_images)

@@ -371,3 +371,295 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
         stats.update(wall_s=time.perf_counter() - t_start, reader_busy_s=t_read[0], writer_busy_s=t_write[0],
                      gpu_loop_waited_for_input_s=t_wait_in, batches=n_batches, depth=depth, lanes=lanes)
     return out
+
+
+# =========================================================================== multi-window recordings
+# The per-file driver (`run_detection`) makes one model call per group of `bs` windows of one file.  The recording route runs the
+# same calls as SEGMENTS of one graph-replayed launch of `batch` windows: segment k of a file = its windows [k*bs, (k+1)*bs), the
+# proposal counts coupled within the segment only (`NbmModel.detect(..., segments=...)`), so every window comes out as the
+# per-file driver's call computes it, while windows of several files fill one launch.
+
+RECORDING_RATES = (22050, 44100)
+
+
+def recording_windows(sr, n, w_pix=1024, hop_img=819, hop=int(44100 * 0.003), max_chunk=int(5e7)):
+    """Number of spectrogram windows of a mono file of n samples at `sr` (prepare_dataset.py:267, per-chunk frame counts of the
+    STFT above 5e7 samples like SpectrogramFrontEnd.spectrogram_db)."""
+    n44 = n * (2 if sr * 2 == 44100 else 1)
+    if n44 < max_chunk:
+        L = 1 + n44 // hop
+    else:
+        L = sum(1 + (min(n44, (k + 1) * max_chunk) - k * max_chunk) // hop for k in range(int(n44 / max_chunk) + 1))
+    return max(1, int(1 + np.ceil((L - w_pix) / hop_img)))
+
+
+def recording_files(files):
+    """Splits a file list into the files the recording route takes -- mono 16-bit PCM at 22.05 or 44.1 kHz, not longer than
+    the 1.5e8-sample limit past which the reference splits the file (process_long_file) -- as [(file, windows)], and the rest
+    (other formats, unreadable headers, longer files), which stays with the per-file driver."""
+    take, rest = [], []
+    max_l = int(15e7) - int(15e7) % 44100
+    for f in files:
+        try:
+            tag, nch, sr, bits, n, _ = wav_header(f)
+        except (OSError, ValueError, struct.error):
+            rest.append(f)
+            continue
+        n44 = n * (2 if sr == 22050 else 1)
+        if tag == 1 and nch == 1 and bits == 16 and sr in RECORDING_RATES and 0 < n44 <= max_l:
+            take.append((f, recording_windows(sr, n)))
+        else:
+            rest.append(f)
+    return take, rest
+
+
+class SegmentPacker:
+    """Packs the segments of successive files into replays of `batch` window slots.  A segment (one model call of the per-file
+    driver: windows [k*bs, min((k+1)*bs, n_img)) of a file) is never split across two replays; a replay that cannot take the
+    next segment whole is closed and its free slots padded.  Replays are lists of (file key, first window, window count)."""
+
+    def __init__(self, batch, bs):
+        if bs < 1 or batch < bs:
+            raise ValueError(f'a replay of {batch} windows cannot hold a segment of {bs}: the recording route needs batch >= bs')
+        self.batch, self.bs = int(batch), int(bs)
+        self.cur, self.fill = [], 0
+
+    def add(self, key, n_img):
+        """-> the replays that became full while the file's segments were placed."""
+        full = []
+        for w0 in range(0, n_img, self.bs):
+            n = min(self.bs, n_img - w0)
+            if self.fill + n > self.batch:
+                full.append(self.cur)
+                self.cur, self.fill = [], 0
+            self.cur.append((key, w0, n))
+            self.fill += n
+        return full
+
+    def flush(self):
+        """-> [the last, partly filled replay] or []."""
+        out = [self.cur] if self.cur else []
+        self.cur, self.fill = [], 0
+        return out
+
+    @staticmethod
+    def segment_sizes(replay, batch):
+        """Segment sizes of a replay in slot order, every padding slot a segment of its own."""
+        sizes = [n for _, _, n in replay]
+        return sizes + [1] * (batch - sum(sizes))
+
+
+class RecordingDetector(GraphedDetector):
+    """Captures `window-table gather -> model.detect(..., segments=...)` for a fixed (batch, min_score) and replays it.
+
+    Static graph inputs: `table` (int64 [batch, ops.WINDOW_ENTRY_WORDS], one `ops.window_entry` per slot: the dB plane, min/max,
+    last-window columns and window index of a file; zero rows are padding) and `seg` (the int32 [2, batch] segment table).  The
+    planes are ordinary device tensors whose addresses travel in the table, so windows of files of any length share a replay
+    without an image tensor per file.  One stream, no forked branches (one lane): the HIP runtime has been seen to crash
+    replaying graphs with parallel branches.  Census check, lane claim and hold rules are GraphedDetector's."""
+
+    def __init__(self, model, batch, min_score=0.2, nms_thresh=0.3, device='cuda'):
+        from . import ops
+        self.model, self.batch, self.lanes = model.eval(), int(batch), 1
+        self.fe = SpectrogramFrontEnd(device)
+        self.fes = [self.fe]
+        self.min_score, self.nms_thresh = min_score, nms_thresh
+        self.table = torch.zeros((self.batch, ops.WINDOW_ENTRY_WORDS), dtype=torch.int64, device=device)
+        self.seg = ops.segment_table([1] * self.batch, device)
+        self.stream = torch.cuda.Stream()
+        self.side = []
+        self.lane_ids = self._claim_lanes(self, 1)
+        try:
+            self._capture(ops)
+        except BaseException:
+            self.close()
+            raise
+
+    def _run(self, k=0):
+        from . import ops
+        fe = self.fe
+        imgs = ops.spec_windows_table(self.table, fe.H_PIX, fe.W_PIX, fe.HOP_SPECTRO)
+        return self.model.detect(imgs[:, None], self.nms_thresh, self.min_score, segments=self.seg)
+
+    def close(self):
+        super().close()
+        self.table = self.seg = None
+
+
+def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=None, write_txt=True, keep_results=True,
+                      stats=None, detector=None, depth=4):
+    """Detects over mono 16-bit PCM recordings of any number of windows (`recording_files`) through one captured graph:
+    -> list of per-file output dicts in `files` order, each exactly `run_detection(model, cfg, f, ..., bs=bs)`'s (None for
+    keep_results=False and for rejected files); `<wav>.txt = str(dict)` written when `write_txt`.
+
+        reader thread   wav -> pinned int16 buffer                     (at most `depth` files ahead)
+        main thread     per file: H2D, spectrogram_db + column map on the graph's stream; its segments go to the SegmentPacker;
+                        per full replay: window / segment tables H2D -> replay -> the slots' rows D2D into each file's row
+                        buffer; per finished file: merge_device_async + D2H into pinned memory, an event behind it
+        writer thread   waits for a file's event -> dict -> txt
+
+    Everything the GPU does runs on one stream in issue order, so a dB plane or row buffer released by the host after its
+    last use is only handed out again to work queued behind that use.  At most 3 replays are in flight.
+    A file the reader cannot decode as mono PCM16 at 22.05 / 44.1 kHz (or whose front end refuses it) is skipped and listed in
+    stats['rejected'] for the per-file driver.  `stats` (dict) also receives counts and stage times.  `detector`: a
+    RecordingDetector to reuse (same batch / min_score)."""
+    from . import ops
+    from .nbm_datasets.prepare_dataset import read_wav_pcm16
+    from .run_detection import merge_device_async, rows_to_output, species_names
+    from types import SimpleNamespace
+    if not files:
+        if stats is not None:
+            stats.update(files=0, windows=0, replays=0, padded_slots=0, shared_replays=0, rejected=[])
+        return []
+    packer = SegmentPacker(batch, bs)
+    det = detector or RecordingDetector(model, batch, min_score=min_score)
+    own_det = detector is None
+    if det.batch != batch or det.min_score != min_score:
+        raise ValueError('the RecordingDetector handed in was captured for another batch / min_score')
+    fe, stream, num_classes = det.fe, det.stream, model.args.num_classes
+    names = species_names(bird_dict or {})
+    out = [None] * len(files)
+    rejected, err = [], []
+    read_q, done_q = queue.Queue(maxsize=max(1, depth)), queue.Queue()
+    t_read, t_write = [0.0], [0.0]
+    stop = threading.Event()
+
+    def reader():
+        try:
+            for i, f in enumerate(files):
+                if stop.is_set():
+                    break
+                t0 = time.perf_counter()
+                try:
+                    x, sr = read_wav_pcm16(f)
+                    if sr not in RECORDING_RATES or len(x) == 0:
+                        raise ValueError(f'{f}: {sr} Hz / {len(x)} samples is not a recording the route takes')
+                    pin = torch.empty((1, len(x)), dtype=torch.int16, pin_memory=True)
+                    pin.numpy()[0] = x
+                except (OSError, ValueError, NotImplementedError, struct.error):
+                    rejected.append(f)
+                    continue
+                finally:
+                    t_read[0] += time.perf_counter() - t0
+                read_q.put((i, pin, sr))
+        except BaseException as exc:                 # noqa: BLE001 -- handed to the main thread
+            err.append(exc)
+        finally:
+            read_q.put(None)
+
+    def writer():
+        try:
+            while True:
+                item = done_q.get()
+                if item is None:
+                    return
+                i, host, ev = item
+                ev.synchronize()
+                t0 = time.perf_counter()
+                res = rows_to_output(ops.unpack_merged(host), num_classes, names)
+                if keep_results:
+                    out[i] = res
+                if write_txt:
+                    with open(txt_path(files[i]), 'w') as fh:
+                        fh.write(str(res))
+                t_write[0] += time.perf_counter() - t0
+        except BaseException as exc:                 # noqa: BLE001
+            err.append(exc)
+
+    live = {}              # file index -> dict(fp, rows, n, left, keep = tensors the queued work reads)
+    inflight = []
+    n_rep, n_pad, n_win, n_files, n_shared = 0, 0, 0, 0, 0
+    t_fe, t_wait = 0.0, 0.0
+    cap = det.det.shape[1]
+
+    def launch(replay):
+        nonlocal n_rep, n_pad, n_shared
+        n_shared += len({key for key, _, _ in replay}) > 1
+        table = np.zeros((batch, ops.WINDOW_ENTRY_WORDS), dtype=np.int64)
+        slot = 0
+        for key, w0, n in replay:
+            r = live[key]
+            for w in range(w0, w0 + n):
+                table[slot] = ops.window_entry(r['db'], r['mm'], r['cols'], w, r['n_img'])
+                slot += 1
+        n_pad += batch - slot
+        det.table.copy_(torch.from_numpy(table).pin_memory(), non_blocking=True)
+        det.seg.copy_(ops.segment_table(SegmentPacker.segment_sizes(replay, batch), 'cpu').pin_memory(), non_blocking=True)
+        det.replay()
+        slot = 0
+        for key, w0, n in replay:
+            r = live[key]
+            r['rows'][w0:w0 + n].copy_(det.det[slot:slot + n])
+            r['n'][w0:w0 + n].copy_(det.n_det[slot:slot + n])
+            slot += n
+            r['left'] -= n
+            if r['left'] == 0:
+                finish(key)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        inflight.append(ev)
+        n_rep += 1
+
+    def finish(key):
+        r = live.pop(key)
+        fp = SimpleNamespace(W_PIX=fe.W_PIX, HOP_SPECTRO=fe.HOP_SPECTRO, spectrogram_length=r['L'])
+        buf = merge_device_async(fp, r['rows'], r['n'], num_classes)
+        host = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=True)
+        host.copy_(buf, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        done_q.put((key, host, ev))
+
+    th_r, th_w = threading.Thread(target=reader, daemon=True), threading.Thread(target=writer, daemon=True)
+    t_start = time.perf_counter()
+    th_r.start(), th_w.start()
+    try:
+        with torch.no_grad(), torch.cuda.stream(stream):
+            while not err:
+                t0 = time.perf_counter()
+                item = read_q.get()
+                t_wait += time.perf_counter() - t0
+                if item is None:
+                    break
+                i, pin, sr = item
+                t0 = time.perf_counter()
+                try:
+                    db, mm, Ls = fe.spectrogram_db(pin.to('cuda', non_blocking=True), sr)
+                except (ValueError, NotImplementedError):      # e.g. a length the reference's chunked STFT fails on
+                    rejected.append(files[i])
+                    continue
+                L = int(sum(Ls))
+                n_img, cols = fe.last_window_columns(Ls)
+                live[i] = dict(db=db[0], mm=mm[0], cols=cols, n_img=n_img, L=L, left=n_img,
+                               rows=torch.empty((n_img, cap, 6), device=db.device, dtype=torch.float32),
+                               n=torch.empty((n_img,), device=db.device, dtype=torch.int32))
+                n_win += n_img
+                n_files += 1
+                t_fe += time.perf_counter() - t0
+                for replay in packer.add(i, n_img):
+                    launch(replay)
+                    while len(inflight) > 2:                   # keep the host at most 3 replays ahead of the GPU
+                        inflight.pop(0).synchronize()
+            if not err:
+                for replay in packer.flush():
+                    launch(replay)
+    finally:
+        stop.set()
+        while th_r.is_alive():                                # unblock a reader waiting for room in the queue
+            try:
+                read_q.get_nowait()
+            except queue.Empty:
+                pass
+            th_r.join(timeout=0.05)
+        done_q.put(None)
+        th_w.join()
+        if own_det:
+            torch.cuda.synchronize()
+            det.close()
+    if err:
+        raise err[0]
+    if stats is not None:
+        stats.update(files=n_files, windows=n_win, replays=n_rep, padded_slots=n_pad, shared_replays=n_shared, rejected=sorted(rejected),
+                     wall_s=time.perf_counter() - t_start, reader_busy_s=t_read[0], writer_busy_s=t_write[0],
+                     front_end_host_s=t_fe, main_waited_for_reader_s=t_wait, batch=batch, bs=bs)
+    return out

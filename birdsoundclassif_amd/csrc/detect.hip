@@ -58,6 +58,13 @@ __global__ void rpn_decode_kernel(const float* __restrict__ cls, const float* __
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(keep_count + b, __popcll(m));
 }
 
+// Segment of image b in a table of contiguous segments: seg[b] = first image, seg[B + b] = image count.  Clamped into
+// [0, B) with b inside it, so that a malformed table can never make a kernel read past the batch.
+__device__ __forceinline__ void seg_range(const int* __restrict__ seg, int B, int b, int& lo, int& hi) {
+  lo = min(max(seg[b], 0), b);
+  hi = max(min(lo + seg[B + b], B), b + 1);
+}
+
 // ------------------------------------------------------------------ top-N selection (radix select + bitonic sort)
 // composite key = (score_key << 32) | ~index : unique, descending order == (score desc, index asc)
 constexpr int SEL_THREADS = 1024;
@@ -65,7 +72,7 @@ constexpr int SEL_THREADS = 1024;
 __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(
     const float* __restrict__ boxes, const uint32_t* __restrict__ keys, const int* __restrict__ keep_count, int B,
     int KA, int top_n, int fail_below, int cap, float* __restrict__ sel_boxes, float* __restrict__ sel_scores,
-    int* __restrict__ n_sel, int per_image) {
+    int* __restrict__ n_sel, int per_image, const int* __restrict__ seg) {
   extern __shared__ unsigned long long sm[];  // [cap] sort buffer, then 256 histogram counters + scalars
   unsigned long long* buf = sm;
   unsigned int* hist = reinterpret_cast<unsigned int*>(sm + cap);
@@ -77,13 +84,15 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(
   if (tid == 0) {
     // layers.py:287: pre_nms_topN = min(topN, min over the BATCH of the kept-anchor counts).  per_image: every image is a
     // batch of its own (bulk inference: the reference CLI runs one file per model call), n_sel[b]
+    // seg: the images of b's segment form one model call of their own (nbm_rpn_select_seg), n_sel[b]
     int mn = 0x7fffffff;
-    if (per_image) mn = keep_count[b];
+    if (seg) { int lo, hi; seg_range(seg, B, b, lo, hi); for (int i = lo; i < hi; ++i) mn = min(mn, keep_count[i]); }
+    else if (per_image) mn = keep_count[b];
     else for (int i = 0; i < B; ++i) mn = min(mn, keep_count[i]);
     int N = min(top_n, mn);
     if (N < fail_below) N = 0;
     s_N = N; s_need = N; s_prefix = 0ull; s_count = 0;
-    if (per_image) n_sel[b] = N; else if (b == 0) n_sel[0] = N;
+    if (per_image || seg) n_sel[b] = N; else if (b == 0) n_sel[0] = N;
   }
   __syncthreads();
   const int N = s_N;
@@ -200,14 +209,16 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const unsigned long long* 
 __global__ void nms_gather_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
                                   const int* __restrict__ keep_idx, const int* __restrict__ keep_cnt, int B, int cap,
                                   int post_n, float* __restrict__ rois, float* __restrict__ roi_scores,
-                                  int* __restrict__ n_out, int per_image) {
+                                  int* __restrict__ n_out, int per_image, const int* __restrict__ seg) {
   const int b = blockIdx.x;
-  // nets_utils.py:236: post_nms_topN = min(topN, min over the BATCH of the survivor counts); per_image: n_out[b]
+  // nets_utils.py:236: post_nms_topN = min(topN, min over the BATCH of the survivor counts); per_image: n_out[b];
+  // seg: min over b's segment, n_out[b]
   int mn = 0x7fffffff;
-  if (per_image) mn = keep_cnt[b];
+  if (seg) { int lo, hi; seg_range(seg, B, b, lo, hi); for (int i = lo; i < hi; ++i) mn = min(mn, keep_cnt[i]); }
+  else if (per_image) mn = keep_cnt[b];
   else for (int i = 0; i < B; ++i) mn = min(mn, keep_cnt[i]);
   const int R = min(post_n, mn);
-  if (threadIdx.x == 0) { if (per_image) n_out[b] = R; else if (b == 0) n_out[0] = R; }
+  if (threadIdx.x == 0) { if (per_image || seg) n_out[b] = R; else if (b == 0) n_out[0] = R; }
   for (int r = threadIdx.x; r < post_n; r += blockDim.x) {
     float* o = rois + ((long long)b * post_n + r) * 4;
     if (r < R) {
@@ -592,34 +603,68 @@ extern "C" int nbm_rpn_decode(const float* cls, const float* reg, const float* a
   return nbm_launch_status();
 }
 
-extern "C" int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
-                              int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel, int per_image,
-                              void* stream) {
+namespace {
+
+int rpn_select_launch(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA, int top_n,
+                      int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel, int per_image, const int* seg,
+                      void* stream) {
   if (!boxes || !keys || !keep_count || !sel_boxes || !sel_scores || !n_sel || B <= 0 || KA <= 0) return NBM_EINVAL;
   if (cap < top_n || cap > 4096 || (cap & (cap - 1))) return NBM_EINVAL;
   const size_t shmem = (size_t)cap * 8 + 256 * 4;
   hipLaunchKernelGGL(rpn_select_kernel, dim3(B), dim3(SEL_THREADS), shmem, (hipStream_t)stream, boxes, keys,
-                     keep_count, B, KA, top_n, fail_below, cap, sel_boxes, sel_scores, n_sel, per_image ? 1 : 0);
+                     keep_count, B, KA, top_n, fail_below, cap, sel_boxes, sel_scores, n_sel, per_image ? 1 : 0, seg);
   return nbm_launch_status();
 }
 
-extern "C" int nbm_nms_batched(const float* boxes, const float* scores, const int* n_in, int B, int cap,
-                               float thresh, int post_n, uint64_t* mask_ws, int* keep_ws, float* rois,
-                               float* roi_scores, int* n_out, int per_image, void* stream) {
+int nms_batched_launch(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh, int post_n,
+                       uint64_t* mask_ws, int* keep_ws, float* rois, float* roi_scores, int* n_out, int per_image,
+                       const int* seg, void* stream) {
   if (!boxes || !scores || !n_in || !mask_ws || !keep_ws || !rois || !roi_scores || !n_out || B <= 0) return NBM_EINVAL;
   if (cap <= 0 || cap > 4096 || (cap & 63) || post_n <= 0 || post_n > cap) return NBM_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const int words = cap / 64;
   int* keep_idx = keep_ws;
   int* keep_cnt = keep_ws + (size_t)B * cap;
-  const int ns = per_image ? 1 : 0;
+  const int ns = (per_image || seg) ? 1 : 0;
   hipLaunchKernelGGL(nms_mask_kernel, dim3(words, words, B), dim3(64), 0, st, boxes, n_in, ns, cap, words, thresh,
                      reinterpret_cast<unsigned long long*>(mask_ws));
   hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(64), 0, st, reinterpret_cast<const unsigned long long*>(mask_ws),
                      n_in, ns, cap, words, keep_idx, keep_cnt);
   hipLaunchKernelGGL(nms_gather_kernel, dim3(B), dim3(256), 0, st, boxes, scores, keep_idx, keep_cnt, B, cap, post_n,
-                     rois, roi_scores, n_out, ns);
+                     rois, roi_scores, n_out, ns, seg);
   return nbm_launch_status();
+}
+
+}  // namespace
+
+extern "C" int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
+                              int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel, int per_image,
+                              void* stream) {
+  return rpn_select_launch(boxes, keys, keep_count, B, KA, top_n, fail_below, cap, sel_boxes, sel_scores, n_sel, per_image,
+                           nullptr, stream);
+}
+
+extern "C" int nbm_rpn_select_seg(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
+                                  int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel,
+                                  const int* seg, void* stream) {
+  if (!seg) return NBM_EINVAL;
+  return rpn_select_launch(boxes, keys, keep_count, B, KA, top_n, fail_below, cap, sel_boxes, sel_scores, n_sel, 0, seg,
+                           stream);
+}
+
+extern "C" int nbm_nms_batched(const float* boxes, const float* scores, const int* n_in, int B, int cap,
+                               float thresh, int post_n, uint64_t* mask_ws, int* keep_ws, float* rois,
+                               float* roi_scores, int* n_out, int per_image, void* stream) {
+  return nms_batched_launch(boxes, scores, n_in, B, cap, thresh, post_n, mask_ws, keep_ws, rois, roi_scores, n_out,
+                            per_image, nullptr, stream);
+}
+
+extern "C" int nbm_nms_batched_seg(const float* boxes, const float* scores, const int* n_in, int B, int cap,
+                                   float thresh, int post_n, uint64_t* mask_ws, int* keep_ws, float* rois,
+                                   float* roi_scores, int* n_out, const int* seg, void* stream) {
+  if (!seg) return NBM_EINVAL;
+  return nms_batched_launch(boxes, scores, n_in, B, cap, thresh, post_n, mask_ws, keep_ws, rois, roi_scores, n_out, 0,
+                            seg, stream);
 }
 
 extern "C" int nbm_roi_pool(const nbm_roi_desc* d, void* stream) {

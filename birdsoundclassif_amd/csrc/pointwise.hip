@@ -125,6 +125,32 @@ __global__ void spec_windows_kernel(const float* __restrict__ db, long long db_b
   }
 }
 
+// nbm_spec_windows for one window per slot, each named by an entry of a device table (the windows of a batch may come from
+// files of different lengths).  The arithmetic per pixel is spec_windows_kernel's, so a window is bit-identical to the one
+// nbm_spec_windows cuts from the same plane.  A slot without a plane (db == NULL) is zeroed; a column outside the plane
+// (a malformed entry) reads as 0 instead of faulting.
+__global__ void spec_windows_table_kernel(const nbm_window_entry* __restrict__ table, int n_bins, float* __restrict__ img,
+                                          int w_pix, int hop_img) {
+  const int b = blockIdx.y;
+  const nbm_window_entry e = table[b];
+  float* dst = img + (long long)b * n_bins * w_pix;
+  const long long total = (long long)n_bins * w_pix;
+  const long long i0 = blockIdx.x * (long long)blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+  if (!e.db || e.window < 0 || e.window >= e.n_img) {
+    for (long long i = i0; i < total; i += step) dst[i] = 0.f;
+    return;
+  }
+  const float lo = nbm_key2f(e.minmax[0]), hi = nbm_key2f(e.minmax[1]);
+  const float range = hi - lo;
+  const int start = e.window * hop_img;
+  const bool last = e.window == e.n_img - 1;
+  for (long long i = i0; i < total; i += step) {
+    const int f = (int)(i / w_pix), c = (int)(i - (long long)f * w_pix);
+    const int col = last ? e.last_cols[c] : start + c;
+    dst[i] = (col >= 0 && col < e.n_frames) ? (e.db[(long long)f * e.db_ld + col] - lo) / range : 0.f;
+  }
+}
+
 // ------------------------------------------------------------------ detector point-wise stages
 __global__ void init_conv_kernel(const float* __restrict__ x, long long n_pix, const float* __restrict__ w,
                                  const float* __restrict__ b, int C, float* __restrict__ y) {
@@ -530,6 +556,14 @@ extern "C" int nbm_spec_windows(const float* db, int64_t db_bs, int db_ld, int b
   dim3 grid(grid_for((long long)n_bins * w_pix, TPB, 512), n_img, batch);
   hipLaunchKernelGGL(spec_windows_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, db, (long long)db_bs, db_ld,
                      n_bins, minmax, img, n_img, w_pix, hop_img, last_cols);
+  return nbm_launch_status();
+}
+
+extern "C" int nbm_spec_windows_table(const nbm_window_entry* table, int batch, int n_bins, float* img, int w_pix,
+                                      int hop_img, void* stream) {
+  if (!table || !img || batch <= 0 || n_bins <= 0 || w_pix <= 0 || hop_img <= 0) return NBM_EINVAL;
+  dim3 grid(grid_for((long long)n_bins * w_pix, TPB, 512), batch);
+  hipLaunchKernelGGL(spec_windows_table_kernel, grid, dim3(TPB), 0, (hipStream_t)stream, table, n_bins, img, w_pix, hop_img);
   return nbm_launch_status();
 }
 

@@ -4,7 +4,10 @@ outputs; `bird_dict.json` is looked up in the CWD like the reference, or given w
 Route: files that are equal-length single-window clips (mono 16-bit PCM, 22.05 / 44.1 kHz, <= 3.06 s: `bulk.bulk_groups`) go
 through the pipelined hipGraph loop of `bulk.detect_files` in batches of --bulk_batch, every clip an independent batch of one --
 exactly what the reference's per-file loop computes for them; everything else (long recordings, other formats) goes through the
-per-file `run_detection` driver with --batch windows per model call, like the reference.  --no_bulk forces the per-file driver.
+per-file `run_detection` driver with --batch windows per model call, like the reference -- or, when the mono PCM16 recordings
+among them (plus clip groups too small for the clip route) hold at least RECORDINGS_MIN_WINDOWS windows, through the graph-replayed
+recording route `bulk.detect_recordings`: the same --batch-window model calls as segments of --bulk_batch-window launches.
+--no_bulk forces the per-file driver.
 Multi-GPU: launch one process per GPU (torchrun); files are sharded `files[rank::world]`, no collective."""
 import argparse
 import glob
@@ -12,6 +15,7 @@ import json
 import os
 
 BULK_MIN_FILES = 8          # below this a graph capture (3 batch-sized steps) costs more than it saves
+RECORDINGS_MIN_WINDOWS = 256   # the recording route's capture (3 launches of --bulk_batch windows) pays off past a few launches
 
 
 def main(argv=None):
@@ -33,11 +37,12 @@ def main(argv=None):
     files = sorted(glob.glob(os.path.join(args.audio_dir, '*.wav')))[rank::world]
     groups, rest = ({}, files) if args.no_bulk else bulk.bulk_groups(files)
     done = 0
+    bird_dict = None
     if groups:
         with open(args.bird_dict, 'r') as f:
             bird_dict = json.load(f)
-        if getattr(config, 'tf_rcnn', False):       # per-image RoI counts are not built for the transformer head
-            rest, groups = sorted(rest + [f for g in groups.values() for f in g]), {}
+    if getattr(config, 'tf_rcnn', False):           # per-image RoI counts are not built for the transformer head
+        rest, groups = sorted(rest + [f for g in groups.values() for f in g]), {}
     for key, group in sorted(groups.items()):
         if len(group) < BULK_MIN_FILES:
             rest.extend(group)
@@ -61,6 +66,26 @@ def main(argv=None):
             continue
         done += len(group)
         print(f'{done} / {len(files)} processed~ (bulk route: {len(group)} clips of {key[1]} samples @ {key[0]} Hz)')
+    if not args.no_bulk and not getattr(config, 'tf_rcnn', False):
+        take, others = bulk.recording_files(sorted(rest))
+        if sum(w for _, w in take) >= RECORDINGS_MIN_WINDOWS:
+            take = [f for f, _ in take]
+            if bird_dict is None:
+                with open(args.bird_dict, 'r') as f:
+                    bird_dict = json.load(f)
+            stats = {}
+            try:
+                bulk.detect_recordings(model, take, batch=max(args.bulk_batch, args.batch), bs=args.batch,
+                                       min_score=args.min_score, bird_dict=bird_dict, write_txt=True, keep_results=False,
+                                       stats=stats)
+                rest = others + stats['rejected']
+                done += len(take) - len(stats['rejected'])
+                print(f'{done} / {len(files)} processed~ (recording route: {stats["windows"]} windows of '
+                      f'{len(take) - len(stats["rejected"])} files in {stats["replays"]} launches)')
+            except (ValueError, NotImplementedError, OSError, torch.cuda.OutOfMemoryError) as exc:
+                # the per-file driver (= the reference's behaviour) takes them all and rewrites what the route finished
+                torch.cuda.empty_cache()
+                print(f'recording route gave up on {len(take)} files ({type(exc).__name__}: {exc}); they go through the per-file driver')
     for wav_path in sorted(rest):
         output = run_detection(model, config, wav_path, args.bird_dict, min_score=args.min_score, bs=args.batch)
         done += 1

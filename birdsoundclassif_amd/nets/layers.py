@@ -183,9 +183,11 @@ class ProposalLayer(nn.Module):
             self._anchors[key] = torch.from_numpy((a + s).reshape(-1, 4).astype(np.float32)).to(device)
         return self._anchors[key]
 
-    def forward_device(self, cls_nhwc, reg_nhwc, independent=False):
+    def forward_device(self, cls_nhwc, reg_nhwc, independent=False, segments=None):
         """-> (rois [B,post_n,4], scores [B,post_n], n_roi int32[1] on device); n_roi = 0 <=> "RPN failed".
-        `independent`: n_roi int32 [B], the batch-coupled minima of layers.py:287 / nets_utils.py:236 taken per image."""
+        `independent`: n_roi int32 [B], the batch-coupled minima of layers.py:287 / nets_utils.py:236 taken per image.
+        `segments` (int32 [2, B] device table, `ops.segment_table`): n_roi int32 [B], the minima (and the "RPN failed" rule)
+        taken per segment -- each segment one model call of the reference."""
         cfg = self.config
         B, h, w, c2 = cls_nhwc.shape
         n_anchor = c2 // 2
@@ -195,8 +197,8 @@ class ProposalLayer(nn.Module):
         boxes, keys, cnt = ops.rpn_decode(cls_nhwc, reg_nhwc, anchors, n_anchor, cfg.img_width, cfg.img_height,
                                           cfg.min_threshold)
         cap = _pow2_cap(pre)
-        sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, cfg.rcnn_batch_size, cap, per_image=independent)
-        return ops.nms_batched(sb, ss, n_sel, cfg.nms_thresh, post)
+        sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, cfg.rcnn_batch_size, cap, per_image=independent, segments=segments)
+        return ops.nms_batched(sb, ss, n_sel, cfg.nms_thresh, post, segments=segments)
 
     def forward(self, labels_pred, bbox_reg):
         rois, scores, n = self.forward_device(_nhwc(labels_pred), _nhwc(bbox_reg))

@@ -107,15 +107,19 @@ class NbmModel(nn.Module):
         return outputs
 
     @torch.no_grad()
-    def detect(self, samples, nms_thresh=0.3, min_score=0.5, independent=False):
+    def detect(self, samples, nms_thresh=0.3, min_score=0.5, independent=False, segments=None):
         """Sync-free eval forward: -> (det [B,50,6] rows {class,x1,y1,x2,y2,score} sorted by (class, score desc),
         n_det int32 [B]), both on the device.  Used by bulk inference; `forward` wraps it.
         `independent=False`: the reference's semantics for ONE model call on this batch -- the proposal counts are coupled over
         the batch (pre / post-NMS top-N = min over the images, layers.py:287, nets_utils.py:236).  `independent=True`: every
         image is a batch of its own, i.e. the result of B model calls with one image each (what the reference CLI does with B
-        single-window files); the counts live in int32 [B] device tensors."""
+        single-window files); the counts live in int32 [B] device tensors.
+        `segments` (int32 [2, B] device table, `ops.segment_table`; overrides `independent`): the batch is cut into contiguous
+        segments, each the result of one model call on its images alone -- windows of several files, `bs` at a time, in one
+        launch (bulk.detect_recordings)."""
         fpn_out = self._fpn_nhwc(samples, lazy=True)
-        rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, independent=independent)
+        rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, independent=independent and segments is None,
+                                                                       segments=segments)
         return self.head.fast_rcnn.detect_device(fpn_out, rois, n_roi, nms_thresh, min_score)
 
     def forward(self, samples, nms_thresh=0.3, min_score=0.5):

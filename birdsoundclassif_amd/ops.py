@@ -473,6 +473,39 @@ def spec_windows(db, minmax, n_frames, n_img, w_pix, hop_img, last_cols):
     return img
 
 
+WINDOW_ENTRY_WORDS = 5         # struct nbm_window_entry as int64 words: db, minmax, last_cols, (db_ld | n_frames << 32), (window | n_img << 32)
+
+
+def window_entry(db, minmax, last_cols, window, n_img):
+    """One row of a `spec_windows_table` table (np.int64 [5]) for window `window` of the file whose dB plane is db
+    [n_bins, n_frames] (a contiguous view of its own storage, e.g. spectrogram_db(...)[0][0]), min/max int32 [2] and last-window
+    columns int32 [w_pix] (all on the device).  The raw addresses go into the table: the caller keeps these tensors alive until
+    every launch that reads the table has run."""
+    import numpy as np
+    _chk(db, name='db'), _chk(last_cols, torch.int32, 'last_cols')
+    if db.dim() != 2 or db.stride(1) != 1 or minmax.dtype != torch.int32 or minmax.numel() != 2 or not minmax.is_contiguous():
+        raise ValueError('window_entry: db [n_bins, n_frames] with unit column stride, minmax int32 [2]')
+    if not 0 <= window < n_img:
+        raise ValueError('window_entry: window index outside the file')
+    lo = lambda a, b: (int(a) & 0xffffffff) | (int(b) << 32)
+    return np.array([db.data_ptr(), minmax.data_ptr(), last_cols.data_ptr(), lo(db.stride(0), db.shape[1]), lo(window, n_img)],
+                    dtype=np.int64)
+
+
+def spec_windows_table(table, n_bins, w_pix, hop_img, out=None):
+    """table int64 [B, WINDOW_ENTRY_WORDS] on the device (rows from `window_entry`; an all-zero row is a padding slot) ->
+    img [B, n_bins, w_pix]: the windows nbm_spec_windows cuts, bit for bit, padding slots zeroed (nbm_spec_windows_table)."""
+    _chk(table, torch.int64, 'table')
+    if table.dim() != 2 or table.shape[1] != WINDOW_ENTRY_WORDS:
+        raise ValueError(f'window table of shape {tuple(table.shape)}: expected (B, {WINDOW_ENTRY_WORDS})')
+    B = table.shape[0]
+    img = out if out is not None else torch.empty((B, n_bins, w_pix), device=table.device, dtype=torch.float32)
+    _chk(img, name='img')
+    assert tuple(img.shape) == (B, n_bins, w_pix)
+    check(lib().nbm_spec_windows_table(_ptr(table), B, n_bins, _ptr(img), w_pix, hop_img, _stream()), 'nbm_spec_windows_table')
+    return img
+
+
 # --------------------------------------------------------------------------- point-wise stages
 def init_conv(x, w, b):
     """x [B,H,W,1] -> [B,H,W,C]."""
@@ -690,18 +723,51 @@ def per_image_counts(n, B):
     return 1
 
 
-def rpn_select(boxes, keys, keep_count, top_n, fail_below, cap, per_image=False):
+def segment_table(sizes, device='cuda'):
+    """Segment sizes (contiguous, in batch order) -> the int32 [2, B] table of nbm_rpn_select_seg / nbm_nms_batched_seg:
+    row 0 the first image of each image's segment, row 1 the segment's image count (on `device`; 'cpu' for a pinned staging
+    copy)."""
+    first, count = [], []
+    b = 0
+    for n in sizes:
+        n = int(n)
+        if n <= 0:
+            raise ValueError('segments hold at least one image')
+        first += [b] * n
+        count += [n] * n
+        b += n
+    t = torch.tensor([first, count], dtype=torch.int32)
+    return t if device == 'cpu' else t.to(device)
+
+
+def _chk_segments(segments, B):
+    _chk(segments, torch.int32, 'segments')
+    if tuple(segments.shape) != (2, B):
+        raise ValueError(f'segment table of shape {tuple(segments.shape)} for a batch of {B}: expected (2, {B})')
+
+
+def rpn_select(boxes, keys, keep_count, top_n, fail_below, cap, per_image=False, segments=None):
+    """`segments` (int32 [2, B] on the device, `segment_table`): the counts are coupled within each segment only and come
+    back per image, n_sel int32 [B] (nbm_rpn_select_seg)."""
     B, KA = keys.shape
     sel_boxes = torch.empty((B, cap, 4), device=boxes.device, dtype=torch.float32)
     sel_scores = torch.empty((B, cap), device=boxes.device, dtype=torch.float32)
+    if segments is not None:
+        _chk_segments(segments, B)
+        n_sel = torch.empty((B,), device=boxes.device, dtype=torch.int32)
+        check(lib().nbm_rpn_select_seg(_ptr(boxes), _ptr(keys), _ptr(keep_count), B, KA, top_n, fail_below, cap,
+                                       _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), _ptr(segments), _stream()),
+              'nbm_rpn_select_seg')
+        return sel_boxes, sel_scores, n_sel
     n_sel = torch.empty((B if per_image and B > 1 else 1,), device=boxes.device, dtype=torch.int32)
     check(lib().nbm_rpn_select(_ptr(boxes), _ptr(keys), _ptr(keep_count), B, KA, top_n, fail_below, cap,
                                _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), per_image_counts(n_sel, B), _stream()), 'nbm_rpn_select')
     return sel_boxes, sel_scores, n_sel
 
 
-def nms_batched(boxes, scores, n_in, thresh, post_n):
-    """boxes [B,cap,4] in walk order, n_in device int -> rois [B,post_n,4], scores [B,post_n], n_out device int."""
+def nms_batched(boxes, scores, n_in, thresh, post_n, segments=None):
+    """boxes [B,cap,4] in walk order, n_in device int -> rois [B,post_n,4], scores [B,post_n], n_out device int.
+    `segments` (see rpn_select): n_in is int32 [B], the post-NMS truncation is coupled per segment, n_out int32 [B]."""
     _chk(boxes, name='boxes'), _chk(scores, name='scores')
     B, cap = scores.shape
     words = cap // 64
@@ -709,6 +775,16 @@ def nms_batched(boxes, scores, n_in, thresh, post_n):
     keep_ws = torch.empty((B * (cap + 1),), device=boxes.device, dtype=torch.int32)
     rois = torch.empty((B, post_n, 4), device=boxes.device, dtype=torch.float32)
     rs = torch.empty((B, post_n), device=boxes.device, dtype=torch.float32)
+    if segments is not None:
+        _chk_segments(segments, B)
+        _chk(n_in, torch.int32, 'n_in')
+        if n_in.numel() != B:
+            raise ValueError(f'segment-coupled NMS needs one count per image, got {n_in.numel()} for a batch of {B}')
+        n_out = torch.empty((B,), device=boxes.device, dtype=torch.int32)
+        check(lib().nbm_nms_batched_seg(_ptr(boxes), _ptr(scores), _ptr(n_in), B, cap, float(thresh), post_n, _ptr(mask_ws),
+                                        _ptr(keep_ws), _ptr(rois), _ptr(rs), _ptr(n_out), _ptr(segments), _stream()),
+              'nbm_nms_batched_seg')
+        return rois, rs, n_out
     per = per_image_counts(n_in, B)
     n_out = torch.empty((B if per else 1,), device=boxes.device, dtype=torch.int32)
     check(lib().nbm_nms_batched(_ptr(boxes), _ptr(scores), _ptr(n_in), B, cap, float(thresh), post_n, _ptr(mask_ws),

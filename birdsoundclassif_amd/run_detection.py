@@ -100,12 +100,23 @@ def run_detection(model, config, wav_path, bird_dicts_path, min_score=0.5, bs=10
         n_all[s:s + det.shape[0]].copy_(n_det)
     with open(bird_dicts_path, 'r') as f:
         birds_dict = json.load(f)
-    birds_dict.update({'Non bird sound': 0})
-    reverse_dict = {idx: name for name, idx in birds_dict.items()}
     rows = merge_device(fp, det_all, n_all, config.num_classes)
+    return rows_to_output(rows, config.num_classes, species_names(birds_dict))
+
+
+def species_names(birds_dict):
+    """bird_dict.json content {name: id} -> {id: name} with 0 = 'Non bird sound' (reference run_detection.py:60-62)."""
+    birds_dict = dict(birds_dict)
+    birds_dict.update({'Non bird sound': 0})
+    return {idx: name for name, idx in birds_dict.items()}
+
+
+def rows_to_output(rows, num_classes, reverse_dict):
+    """Merged rows (float32 CPU [n,6] {species,x1,y1,x2,y2,score}, `merge_device`) -> the per-file output dictionary of
+    `run_detection`: {species name: {'bbox_coord': [[x1,y1,x2,y2]...], 'scores': [...]}}, species ascending."""
     species = rows[:, 0].to(torch.int64).numpy()
     out = {}
-    for idx in range(1, config.num_classes + 1):
+    for idx in range(1, num_classes + 1):
         m = species == idx
         if m.any():
             sel = rows[torch.from_numpy(m)]
@@ -117,6 +128,13 @@ def merge_device(fp, det, n_det, num_classes, nms_thresh=0.3):
     """`merge_images` on the detector's device rows of one file: det [n_img,cap,6] ({class,x1,y1,x2,y2,score}, sorted by
     (class, score desc) per window), n_det int32 [n_img] -> float32 CPU rows [n,6] {species,x1,y1,x2,y2,score} in the kept
     (class-major) order.  Collect, NMS and gather are queued without a host sync; one copy brings the result back."""
+    return ops.unpack_merged(merge_device_async(fp, det, n_det, num_classes, nms_thresh))
+
+
+def merge_device_async(fp, det, n_det, num_classes, nms_thresh=0.3):
+    """The device half of `merge_device`: -> the device buffer of `ops.merge_gather` (`ops.unpack_merged` reads it).  No host
+    sync for any file the per-file driver takes (<= 1.5e8 samples).  `fp`: anything with W_PIX, HOP_SPECTRO,
+    spectrogram_length."""
     boxes, scores, species, n = ops.merge_collect(det, n_det, fp.W_PIX, fp.HOP_SPECTRO, fp.spectrogram_length, num_classes)
     cap = boxes.shape[0]
     if cap > ops.MERGE_MAX_N:
@@ -125,7 +143,7 @@ def merge_device(fp, det, n_det, num_classes, nms_thresh=0.3):
             raise ValueError(f'{int(n.item())} candidate boxes in one file: the device merge handles up to {ops.MERGE_MAX_N}')
         cap = ops.MERGE_MAX_N
     keep, n_keep = ops.merge_nms(boxes, n, nms_thresh, cap)
-    return ops.unpack_merged(ops.merge_gather(boxes, scores, species, keep, n_keep, cap))
+    return ops.merge_gather(boxes, scores, species, keep, n_keep, cap)
 
 
 def load_model(mod_p):

@@ -294,6 +294,23 @@ int nbm_spec_windows(const float* db, int64_t db_bs, int db_ld, int batch, int n
                      const uint32_t* minmax, float* img, int n_img, int w_pix, int hop_img,
                      const int32_t* last_cols, void* stream);
 
+/* One slot of nbm_spec_windows_table: window `window` (of `n_img`) of one file's dB plane db[n_bins][db_ld] (n_frames
+ * valid columns) with that file's min/max keys (minmax[0..1], as nbm_stft_db writes them) and the column list of its LAST
+ * window (last_cols[w_pix], prepare_dataset.py:window_columns).  db == NULL: a padding slot. */
+typedef struct nbm_window_entry {
+  const float* db;
+  const uint32_t* minmax;
+  const int32_t* last_cols;
+  int32_t db_ld, n_frames, window, n_img;
+} nbm_window_entry;
+
+/* nbm_spec_windows with the windows of a batch named by a device table (one entry per slot, files of any length mixed):
+ * img[b][f][c] = the pixel nbm_spec_windows computes for window table[b].window of table[b]'s file, bit for bit; padding
+ * slots are zeroed.  img: [batch][n_bins][w_pix].  Reads only the table and the planes it names: a captured graph takes a
+ * new batch of windows through a new table. */
+int nbm_spec_windows_table(const nbm_window_entry* table, int batch, int n_bins, float* img, int w_pix, int hop_img,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Point-wise / small-window detector stages (NHWC fp32).
  */
@@ -384,6 +401,14 @@ int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_cou
                    int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel,
                    int per_image, void* stream);
 
+/* nbm_rpn_select with SEGMENT coupling: the batch is cut into contiguous segments, each one model call of the reference
+ * (run_detection.py:40-67: windows [k*bs, (k+1)*bs) of one file).  seg: device int32 [2][B], seg[b] = first image of b's
+ * segment, seg[B + b] = its image count.  N_b = min(top_n, min over b's segment of keep_count), 0 if < fail_below;
+ * n_sel[b] = N_b.  Segments never couple with each other; all-singleton segments give per_image. */
+int nbm_rpn_select_seg(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
+                       int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel,
+                       const int* seg, void* stream);
+
 /* Greedy NMS in the given order (suppress IoU >= thresh, +1 pixel convention) then the batch-coupled
  * truncation R = min(post_n, min_b #keep_b) -- nets_utils.py:189-245.  n_in[0] boxes per image.
  * Workspaces: mask_ws B*cap*(cap/64) uint64, keep_ws B*(cap+1) int32.  Writes rois[b][post_n][4],
@@ -392,6 +417,12 @@ int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_cou
 int nbm_nms_batched(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh,
                     int post_n, uint64_t* mask_ws, int* keep_ws, float* rois, float* roi_scores, int* n_out,
                     int per_image, void* stream);
+
+/* nbm_nms_batched with SEGMENT coupling (seg as in nbm_rpn_select_seg): n_in[b] boxes in image b,
+ * R_b = min(post_n, min over b's segment of #keep), n_out[b] = R_b. */
+int nbm_nms_batched_seg(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh,
+                        int post_n, uint64_t* mask_ws, int* keep_ws, float* rois, float* roi_scores, int* n_out,
+                        const int* seg, void* stream);
 
 /* ROIPooling (layers.py:406-497): level assignment, window, 2x2 adaptive average of the FPN map and of
  * the separable positional encoding.  fmaps: 5 device pointers (NHWC, C channels); pe_f [img_h][C/2],

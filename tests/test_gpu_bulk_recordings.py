@@ -1,0 +1,250 @@
+"""GPU: the recording route (bulk.detect_recordings) -- segment-coupled proposal counts (nbm_rpn_select_seg /
+nbm_nms_batched_seg) against the coupled entry points on each segment alone, NbmModel.detect(segments=...) against one call
+per segment, the window-table front end (nbm_spec_windows_table) against nbm_spec_windows, replays of the captured graph, and
+the CLI on a mixed shard byte for byte against the per-file driver."""
+import ast
+import json
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from birdsoundclassif_amd import bulk, ops, synth                              # noqa: E402
+from birdsoundclassif_amd.nbm_datasets.prepare_dataset import SpectrogramFrontEnd   # noqa: E402
+from birdsoundclassif_amd.train import default_args                            # noqa: E402
+from helpers import filler_state_dict                                          # noqa: E402
+
+LAYOUT = [4, 1, 3, 4, 2]
+NC = 150
+
+
+def _proposal_inputs(B, seed, starved=()):
+    """Decoded-anchor stand-ins: boxes [B,KA,4] that overlap often, uint32 keys (0 = dropped anchor), keep counts."""
+    g = torch.Generator().manual_seed(seed)
+    KA = 6000
+    xy = torch.rand((B, KA, 2), generator=g) * torch.tensor([1000., 360.])
+    wh = 4 + torch.rand((B, KA, 2), generator=g) * torch.tensor([120., 60.])
+    boxes = torch.cat([xy, xy + wh], -1).round()
+    # keys of scores in (0.01, 1) (nbm_f2key of a positive float: its bits with the sign bit set), as int32 storage
+    scores = 0.01 + 0.99 * torch.rand((B, KA), generator=g)
+    keys = scores.view(torch.int32) | torch.tensor(-2 ** 31, dtype=torch.int32)
+    keys[torch.rand((B, KA), generator=g) < 0.6] = 0
+    for b, n in starved:                                     # image b keeps only n anchors
+        nz = keys[b].nonzero().flatten()
+        keys[b, nz[n:]] = 0
+    cnt = (keys != 0).sum(1).to(torch.int32)
+    return boxes.cuda().contiguous(), keys.cuda().contiguous(), cnt.cuda()
+
+
+def _seg_vs_coupled(layout, starved=()):
+    a = default_args(device='cuda')
+    B = sum(layout)
+    boxes, keys, cnt = _proposal_inputs(B, 7 + B, starved)
+    pre, post, fail = a.pre_nms_topN_eval, a.post_nms_topN_eval, a.rcnn_batch_size
+    cap = 1 << (pre - 1).bit_length()
+    seg = ops.segment_table(layout)
+    sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, fail, cap, segments=seg)
+    rois, rs, n_out = ops.nms_batched(sb, ss, n_sel, a.nms_thresh, post, segments=seg)
+    torch.cuda.synchronize()
+    s = 0
+    for n in layout:
+        sl = slice(s, s + n)
+        sb1, ss1, n1 = ops.rpn_select(boxes[sl].contiguous(), keys[sl].contiguous(), cnt[sl].contiguous(), pre, fail, cap)
+        r1, rs1, no1 = ops.nms_batched(sb1, ss1, n1, a.nms_thresh, post)
+        assert torch.equal(sb[sl], sb1) and torch.equal(ss[sl], ss1)
+        assert torch.equal(n_sel[sl], n1.expand(n)), (s, n_sel[sl].tolist(), n1.tolist())
+        assert torch.equal(rois[sl], r1) and torch.equal(rs[sl], rs1)
+        assert torch.equal(n_out[sl], no1.expand(n)), (s, n_out[sl].tolist(), no1.tolist())
+        s += n
+    return n_sel.cpu(), n_out.cpu(), fail
+
+
+def test_segment_counts_equal_coupled_calls_per_segment():
+    # image 4 (a segment of its own) and image 10 (in segment [8, 12)) keep few anchors: their segments' pre-NMS counts drop
+    n_sel, n_out, _ = _seg_vs_coupled(LAYOUT, starved=[(4, 120), (10, 300)])
+    assert (n_out > 0).all()
+    # the segments really differ: coupling over the whole launch would have given one count
+    assert n_sel[4] == 120 and n_sel[8:12].tolist() == [300] * 4 and len(set(n_sel.tolist())) == 3
+
+
+def test_segment_below_fail_threshold_fails_alone():
+    # image 6 (inside the 3-image segment [5, 8)) keeps fewer anchors than rcnn_batch_size: that segment's RPN fails, no other
+    a = default_args(device='cuda')
+    n_sel, n_out, fail = _seg_vs_coupled(LAYOUT, starved=[(6, a.rcnn_batch_size - 3)])
+    assert n_sel[5:8].tolist() == [0, 0, 0] and n_out[5:8].tolist() == [0, 0, 0]
+    assert (n_sel[:5] >= fail).all() and (n_sel[8:] >= fail).all() and (n_out[:5] > 0).all() and (n_out[8:] > 0).all()
+
+
+def test_singleton_segments_equal_per_image():
+    a = default_args(device='cuda')
+    B = 9
+    boxes, keys, cnt = _proposal_inputs(B, 99, starved=[(3, 5)])
+    pre, post, fail = a.pre_nms_topN_eval, a.post_nms_topN_eval, a.rcnn_batch_size
+    cap = 1 << (pre - 1).bit_length()
+    seg = ops.segment_table([1] * B)
+    got = ops.rpn_select(boxes, keys, cnt, pre, fail, cap, segments=seg)
+    ref = ops.rpn_select(boxes, keys, cnt, pre, fail, cap, per_image=True)
+    for x, y in zip(got, ref):
+        assert torch.equal(x, y)
+    got = ops.nms_batched(*got, a.nms_thresh, post, segments=seg)
+    ref = ops.nms_batched(*ref, a.nms_thresh, post)
+    for x, y in zip(got, ref):
+        assert torch.equal(x, y)
+    assert got[2][3].item() == 0 and (got[2] > 0).sum().item() == B - 1
+
+
+# ----------------------------------------------------------------------------------------------- model
+@pytest.fixture(scope='module')
+def model():
+    from birdsoundclassif_amd.nets import build_model
+    m, _ = build_model(default_args(device='cuda'))
+    m.load_state_dict(filler_state_dict())
+    return m.cuda().eval()
+
+
+def _file_windows(fe, pcm, sr):
+    imgs, L = fe(torch.from_numpy(pcm)[None].cuda(), sr)
+    return imgs[0], L
+
+
+def test_detect_with_segments_equals_one_call_per_segment(model):
+    fe = SpectrogramFrontEnd('cuda')
+    w1, _ = _file_windows(fe, synth.clip_pcm16(501, 22050 * 22), 22050)        # 9 windows
+    w2, _ = _file_windows(fe, synth.clip_pcm16(502, 22050 * 12), 22050)        # 5 windows
+    imgs = torch.cat([w1, w2])[:, None].contiguous()
+    layout = [4, 4, 1, 4, 1]                                                   # bs = 4 over each file
+    assert sum(layout) == imgs.shape[0] == 14
+    det, n = model.detect(imgs, 0.3, 0.05, segments=ops.segment_table(layout))
+    det, n = det.clone(), n.clone()
+    s = 0
+    for k in layout:
+        d1, n1 = model.detect(imgs[s:s + k].contiguous(), 0.3, 0.05)
+        assert torch.equal(n[s:s + k], n1), (s, n[s:s + k].tolist(), n1.tolist())
+        for j in range(k):
+            c = int(n1[j])
+            assert torch.equal(det[s + j, :c], d1[j, :c]), (s, j)
+        s += k
+    assert int(n.sum()) > 0
+
+
+# ----------------------------------------------------------------------------------------------- front end
+def _table_windows(fe, pcm, sr, pad=0):
+    """All windows of one file through nbm_spec_windows_table (plus `pad` zero slots in front)."""
+    db, mm, Ls = fe.spectrogram_db(torch.from_numpy(pcm)[None].cuda(), sr)
+    n_img, cols = fe.last_window_columns(Ls)
+    rows = [np.zeros(ops.WINDOW_ENTRY_WORDS, np.int64)] * pad
+    rows += [ops.window_entry(db[0], mm[0], cols, w, n_img) for w in range(n_img)]
+    table = torch.from_numpy(np.stack(rows)).cuda()
+    out = ops.spec_windows_table(table, fe.H_PIX, fe.W_PIX, fe.HOP_SPECTRO)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize('sr,seconds', [(22050, 2.4), (22050, 17.3), (44100, 41.0), (22050, 95.7)])
+def test_window_table_equals_spec_windows(sr, seconds):
+    fe = SpectrogramFrontEnd('cuda')
+    pcm = synth.clip_pcm16(600 + int(seconds), int(sr * seconds), sr)
+    ref, _ = _file_windows(fe, pcm, sr)
+    got = _table_windows(fe, pcm, sr, pad=2)
+    assert torch.equal(got[2:], ref)
+    assert not got[:2].any()
+    if seconds < 3:
+        assert ref.shape[0] == 1
+
+
+def test_window_table_equals_spec_windows_chunked_stft():
+    # above 5e7 samples at 44.1 kHz the STFT runs chunk by chunk and the last window stops at its chunk's end
+    sr, n = 44100, int(5e7) + 3 * 44100 + 777
+    rng = np.random.default_rng(5)
+    pcm = np.clip(rng.normal(0, 900, n) + 4000 * np.sin(np.arange(n) * 0.21), -32768, 32767).astype(np.int16)
+    fe = SpectrogramFrontEnd('cuda')
+    ref, L = _file_windows(fe, pcm, sr)
+    assert ref.shape[0] == bulk.recording_windows(sr, n) > 450
+    got = _table_windows(fe, pcm, sr)
+    assert torch.equal(got, ref)
+
+
+# ----------------------------------------------------------------------------------------------- replays
+def test_recording_detector_replays_are_bit_identical_and_kernel_only(model):
+    det = bulk.RecordingDetector(model, 12, min_score=0.05)
+    try:
+        assert {k for k, v in det.census.items() if v} == {'kernel'}, det.census
+        fe = det.fe
+        pcm = synth.clip_pcm16(700, 22050 * 25)
+        db, mm, Ls = fe.spectrogram_db(torch.from_numpy(pcm)[None].cuda(), 22050)
+        n_img, cols = fe.last_window_columns(Ls)
+        assert n_img == 10
+        rows = [ops.window_entry(db[0], mm[0], cols, w, n_img) for w in range(n_img)]
+        rows += [np.zeros(ops.WINDOW_ENTRY_WORDS, np.int64)] * 2
+        with torch.cuda.stream(det.stream):
+            det.table.copy_(torch.from_numpy(np.stack(rows)))
+            det.seg.copy_(ops.segment_table([4, 4, 2, 1, 1], 'cpu'))
+            det.replay()
+            a = (det.det.clone(), det.n_det.clone())
+            det.replay()
+            b = (det.det.clone(), det.n_det.clone())
+        det.stream.synchronize()
+        assert torch.equal(a[1], b[1]) and int(a[1][:10].sum()) > 0
+        for j in range(12):
+            c = int(a[1][j])
+            assert torch.equal(a[0][j, :c], b[0][j, :c])
+    finally:
+        det.close()
+
+
+# ----------------------------------------------------------------------------------------------- end to end
+@pytest.mark.parametrize('bs', [4, 3])
+def test_cli_recording_route_writes_the_same_files_as_the_per_file_driver(tmp_path, monkeypatch, bs):
+    from birdsoundclassif_amd import nbm_detect
+    ck = tmp_path / 'model_weights'
+    ck.mkdir()
+    args = default_args(device='cuda')
+    cfg = {k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in vars(args).items() if k not in ('scales',)}
+    (ck / 'args').write_text(json.dumps(cfg))
+    torch.save({'checkpoints': filler_state_dict(), 'steps': 0, 'epoch': 0, 'best_val_cls_loss': 99}, str(ck / 'model_chkpt.pt'))
+    (tmp_path / 'bird_dict.json').write_text(json.dumps({f'Species {i}': i for i in range(1, NC + 1)}))
+    a, b = tmp_path / 'route', tmp_path / 'perfile'
+    a.mkdir()
+    long_files = {'night.wav': (600, 22050), 'rec_a.wav': (31.7, 22050), 'rec_b.wav': (9.1, 44100), 'rec_c.wav': (64.2, 22050)}
+    for i, (name, (sec, sr)) in enumerate(sorted(long_files.items())):
+        # night.wav: the 10-minute recording of test_gpu_long_recordings, > 4 096 boxes before the merge at min_score 0
+        seed = 4242 if name == 'night.wav' else 800 + i
+        synth.write_wav(str(a / name), synth.clip_pcm16(seed, int(sr * sec), sr), sr)
+    for i, sec in enumerate([2.1, 2.7, 1.3]):                                   # odd-length single-window files
+        synth.write_wav(str(a / f'odd{i}.wav'), synth.clip_pcm16(820 + i, int(22050 * sec)), 22050)
+    for i in range(8):                                                          # equal 3 s clips: the clip route
+        synth.write_wav(str(a / f'clip{i}.wav'), synth.clip_pcm16(830 + i), 22050)
+    for i in range(2):                                                          # a clip group too small for the clip route
+        synth.write_wav(str(a / f'pair{i}.wav'), synth.clip_pcm16(840 + i, 50000), 22050)
+    shutil.copytree(str(a), str(b))
+
+    seen = []
+    real = bulk.detect_recordings
+
+    def spy(model, files, **kw):
+        out = real(model, files, **kw)
+        seen.append((sorted(os.path.basename(f) for f in files), dict(kw['stats']), kw['batch'], kw['bs']))
+        return out
+
+    monkeypatch.setattr(bulk, 'detect_recordings', spy)
+    common = ['--ckpt', str(ck), '--min_score', '0.0', '--batch', str(bs), '--bird_dict', str(tmp_path / 'bird_dict.json')]
+    nbm_detect.main(common + ['--audio_dir', str(a), '--bulk_batch', '22'])
+    nbm_detect.main(common + ['--audio_dir', str(b), '--no_bulk'])
+
+    assert len(seen) == 1
+    files, st, batch, sbs = seen[0]
+    assert (batch, sbs) == (22, bs)
+    assert files == sorted(list(long_files) + [f'odd{i}.wav' for i in range(3)] + ['pair0.wav', 'pair1.wav'])
+    assert st['rejected'] == [] and st['files'] == len(files)
+    assert st['windows'] == sum(bulk.recording_windows(sr, int(sr * sec)) for sec, sr in long_files.values()) + 5
+    assert st['shared_replays'] > 0 and st['padded_slots'] > 0
+    names = sorted(p.name for p in a.glob('*.txt'))
+    assert len(names) == 17 and names == sorted(p.name for p in b.glob('*.txt'))
+    for name in names:
+        assert (a / name).read_text() == (b / name).read_text(), name
+    night = ast.literal_eval((a / 'night.txt').read_text())
+    assert sum(len(v['scores']) for v in night.values()) > 0
