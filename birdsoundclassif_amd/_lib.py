@@ -39,7 +39,7 @@ class RoiDesc(C.Structure):
                 ('n_levels', C.c_int), ('C', C.c_int),
                 ('rois', C.c_void_p), ('n_roi', C.c_void_p), ('B', C.c_int), ('roi_cap', C.c_int),
                 ('pe_f', C.c_void_p), ('pe_t', C.c_void_p), ('img_h', C.c_int), ('img_w', C.c_int),
-                ('pool', C.c_void_p), ('pe', C.c_void_p), ('level', C.c_void_p), ('n_roi_per_image', C.c_int)]
+                ('pool', C.c_void_p), ('pe', C.c_void_p), ('level', C.c_void_p)]
 
 
 class AugmentParams(C.Structure):
@@ -90,12 +90,10 @@ SIGNATURES = {
     'nbm_mha_small': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _L, _L, _P, _F, _P],
     'nbm_pair_softmax': [_P, _L, _I, _I, _P, _I, _P],
     'nbm_rpn_decode': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
-    'nbm_rpn_select': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P],
-    'nbm_nms_batched': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _I, _P],
-    'nbm_rpn_select_seg': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
-    'nbm_nms_batched_seg': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
+    'nbm_rpn_select': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    'nbm_nms_batched': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     'nbm_roi_pool': [C.POINTER(RoiDesc), _P],
-    'nbm_rcnn_post': [_P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _I, _P],
+    'nbm_rcnn_post': [_P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P],
     # ---- per-file merge (run_detection.merge_images)
     'nbm_merge_collect': [_P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P],
     'nbm_merge_nms_workspace': [_I, C.POINTER(C.c_int64)],
@@ -135,7 +133,7 @@ SIGNATURES = {
     'nbm_wino23_conv_fused': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P],
     'nbm_wino23_rows_tiles': [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P],
     'nbm_wino23_conv_fused_tiles': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P],
-    'nbm_roi_tiles': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P],
+    'nbm_roi_tiles': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
     'nbm_wino23_input_tiles': [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P],
     'nbm_wino23_outgrad_tiles': [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P],
     'nbm_cell_outgrad': [_P, _I, _I, _I, _I, _I, _P, _P, _P],

@@ -15,7 +15,8 @@ survivors, RoI count, detections per clip) lives in fixed-capacity device buffer
 The clips of a batch are INDEPENDENT (`NbmModel.detect(..., independent=True)`): the reference CLI runs one file per model call
 (nbm_detect.py:24-28 -> run_detection.py:49-55, a 3 s clip is a batch of one window), so the batch-coupled proposal counts of
 the reference's ProposalLayer / nms (min over the batch, layers.py:287, nets_utils.py:236) must not couple files that merely
-share a launch here: every clip keeps its own counts, exactly as if it had been run alone.
+share a launch here: every clip is a segment of its own (`ops.batch_segments(B, 1)`) and keeps its own counts, exactly as if it
+had been run alone.
 
 Multi-GPU: one process per GPU, files sharded `files[rank::world]`, no data-path collective (`nbm_detect.py` does the sharding).
 """
@@ -453,7 +454,8 @@ class RecordingDetector(GraphedDetector):
     """Captures `window-table gather -> model.detect(..., segments=...)` for a fixed (batch, min_score) and replays it.
 
     Static graph inputs: `table` (int64 [batch, ops.WINDOW_ENTRY_WORDS], one `ops.window_entry` per slot: the dB plane, min/max,
-    last-window columns and window index of a file; zero rows are padding) and `seg` (the int32 [2, batch] segment table).  The
+    last-window columns and window index of a file; zero rows are padding) and `seg` (the int32 [2, batch] segment table, rewritten
+before every replay: a tensor of its own, never one of the shared `ops.batch_segments` tables).  The
     planes are ordinary device tensors whose addresses travel in the table, so windows of files of any length share a replay
     without an image tensor per file.  One stream, no forked branches (one lane): the HIP runtime has been seen to crash
     replaying graphs with parallel branches.  Census check, lane claim and hold rules are GraphedDetector's."""

@@ -21,14 +21,12 @@ class Faster_RCNN(nn.Module):
     def forward_second_stage(self, *args, **kwargs):
         return self.fast_rcnn(*args, **kwargs)
 
-    def forward_first_stage_device(self, fpn_nhwc, independent=False, segments=None):
-        """-> (rois [B,cap,4], roi_scores, n_roi device int32 [1] (or [B] with `independent`: every image a batch of its own;
-        or [B] with `segments`: every segment of the int32 [2, B] table a batch of its own), cls NHWC, reg NHWC, raw cls NHWC);
-        no host sync."""
+    def forward_first_stage_device(self, fpn_nhwc, segments=None):
+        """-> (rois [B,cap,4], roi_scores, n_roi device int32 [B], cls NHWC, reg NHWC, raw cls NHWC); no host sync.  Every
+        segment of `segments` (int32 [2, B] device table; None: the whole batch) is one model call of its own."""
         cls, reg, cls_raw = self.rpn.forward_nhwc(fpn_nhwc)
         with torch.no_grad():
-            rois, scores, n_roi = self.prop_layer.forward_device(cls.detach(), reg.detach(), independent=independent,
-                                                                 segments=segments)
+            rois, scores, n_roi = self.prop_layer.forward_device(cls.detach(), reg.detach(), segments=segments)
         return rois, scores, n_roi, cls, reg, cls_raw
 
     def forward_first_stage(self, fpn_pyramid_out, host_work=None):
@@ -43,7 +41,7 @@ class Faster_RCNN(nn.Module):
             pin = self.__dict__['_n_roi_pin'] = torch.zeros((1,), dtype=torch.int32).pin_memory()
         ev = None
         if n_roi.is_cuda:
-            pin.copy_(n_roi.view(-1)[:1], non_blocking=True)
+            pin.copy_(n_roi[:1], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
         if host_work is not None:           # everything of the first stage is queued; the host is still ahead of the GPU here
@@ -55,7 +53,7 @@ class Faster_RCNN(nn.Module):
             ev.synchronize()
             n = int(pin.item())
         else:
-            n = int(n_roi.item())
+            n = int(n_roi[0].item())
         if n == 0:
             print('Not enough possible RoIs, RPN failed')
             rois = torch.tensor([]).to(cls.device)

@@ -183,11 +183,11 @@ class ProposalLayer(nn.Module):
             self._anchors[key] = torch.from_numpy((a + s).reshape(-1, 4).astype(np.float32)).to(device)
         return self._anchors[key]
 
-    def forward_device(self, cls_nhwc, reg_nhwc, independent=False, segments=None):
-        """-> (rois [B,post_n,4], scores [B,post_n], n_roi int32[1] on device); n_roi = 0 <=> "RPN failed".
-        `independent`: n_roi int32 [B], the batch-coupled minima of layers.py:287 / nets_utils.py:236 taken per image.
-        `segments` (int32 [2, B] device table, `ops.segment_table`): n_roi int32 [B], the minima (and the "RPN failed" rule)
-        taken per segment -- each segment one model call of the reference."""
+    def forward_device(self, cls_nhwc, reg_nhwc, segments=None):
+        """-> (rois [B,post_n,4], scores [B,post_n], n_roi int32 [B] on device); n_roi[b] = 0 <=> "RPN failed".
+        The minima of layers.py:287 / nets_utils.py:236 (and the "RPN failed" rule) are taken per segment of `segments`
+        (int32 [2, B] device table, `ops.segment_table` / `ops.batch_segments`), each segment one model call of the
+        reference; None: the whole batch is one call."""
         cfg = self.config
         B, h, w, c2 = cls_nhwc.shape
         n_anchor = c2 // 2
@@ -197,12 +197,12 @@ class ProposalLayer(nn.Module):
         boxes, keys, cnt = ops.rpn_decode(cls_nhwc, reg_nhwc, anchors, n_anchor, cfg.img_width, cfg.img_height,
                                           cfg.min_threshold)
         cap = _pow2_cap(pre)
-        sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, cfg.rcnn_batch_size, cap, per_image=independent, segments=segments)
+        sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, cfg.rcnn_batch_size, cap, segments=segments)
         return ops.nms_batched(sb, ss, n_sel, cfg.nms_thresh, post, segments=segments)
 
     def forward(self, labels_pred, bbox_reg):
         rois, scores, n = self.forward_device(_nhwc(labels_pred), _nhwc(bbox_reg))
-        n = int(n.item())
+        n = int(n[0].item())
         if n == 0:
             print('Not enough possible RoIs, RPN failed')
             return torch.tensor([]).to(rois.device), torch.tensor([]).to(rois.device)
@@ -226,7 +226,7 @@ class ROIPooling(nn.Module):
         return self._pe[key]
 
     def forward_device(self, rois, n_roi, fmaps_nhwc):
-        """rois [B,cap,4], n_roi device int32[1] -> pool, pe NHWC [B*cap,2,2,C], level int32 [B,cap]."""
+        """rois [B,cap,4], n_roi device int32 [B] -> pool, pe NHWC [B*cap,2,2,C], level int32 [B,cap]."""
         cfg = self.config
         if (cfg.roi_pool_h, cfg.roi_pool_w) != (2, 2):
             raise NotImplementedError('roi_pool 2x2 (reference default) only')
@@ -239,7 +239,7 @@ class ROIPooling(nn.Module):
 
     def forward(self, rois, conv_out):
         B, R = rois.shape[:2]
-        n = torch.full((1,), R, device=rois.device, dtype=torch.int32)
+        n = torch.full((B,), R, device=rois.device, dtype=torch.int32)
         pool, pe, lvl = self.forward_device(rois.contiguous(), n, [_nhwc(f) for f in conv_out])
         C_ = pool.shape[-1]
         return (pool.view(B, R, 2, 2, C_).permute(0, 1, 4, 2, 3), pe.view(B, R, 2, 2, C_).permute(0, 1, 4, 2, 3),
@@ -352,7 +352,8 @@ class Transformer_RCNN(nn.Module):
                 nn.init.xavier_uniform_(p)
 
     def forward_nhwc(self, pool, pe, B, R, n_valid=None):
-        """pool, pe: NHWC [B*R,2,2,C]; n_valid: device int32[1] RoIs per image that are real (pe_qk masks the rest)
+        """pool, pe: NHWC [B*R,2,2,C]; n_valid: device int32, element 0 = RoIs per image that are real
+        (the same count for every image of one model call; pe_qk masks the rest)
         -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc] softmaxed)."""
         if torch.is_grad_enabled() and (self.training or pool.requires_grad):
             return self._forward_train(pool, pe, B, R, n_valid)
@@ -434,8 +435,6 @@ class FastRCNN(nn.Module):
 
     def _head(self, pool, pe, rois, n_roi):
         if self.config.tf_rcnn:
-            if n_roi.numel() != 1:
-                raise NotImplementedError('Transformer_RCNN with per-image RoI counts (independent detection)')
             return self.rcnn.forward_nhwc(pool, pe, rois.shape[0], rois.shape[1], n_roi)
         return self.rcnn.forward_nhwc(pool, pe)
 
@@ -479,7 +478,7 @@ class FastRCNN(nn.Module):
         B, R = rois.shape[:2]
         fm = [_nhwc(f) for f in conv_out]
         rois = rois.contiguous()
-        n = torch.full((1,), R, device=rois.device, dtype=torch.int32)
+        n = torch.full((B,), R, device=rois.device, dtype=torch.int32)
         if training:
             pool, pe, _ = self.roi_pooling.forward_device(rois, n, fm)
             return self._head(pool, pe, rois, n)

@@ -14,6 +14,7 @@ from .fpn import build_fpn
 from . import functional as Fn
 from .self_attention import build_sa_layers, materialize
 from .head import build_head
+from .. import ops
 
 DEFER_PROJECTION_TRAIN = os.environ.get('NBM_DEFER_PROJECTION_TRAIN', '1') != '0'
 DEFER_PROJECTION = os.environ.get('NBM_DEFER_PROJECTION', '1') != '0'      # evaluation mode: attention's final projection folded into the FPN laterals
@@ -117,9 +118,13 @@ class NbmModel(nn.Module):
         `segments` (int32 [2, B] device table, `ops.segment_table`; overrides `independent`): the batch is cut into contiguous
         segments, each the result of one model call on its images alone -- windows of several files, `bs` at a time, in one
         launch (bulk.detect_recordings)."""
+        B = samples.shape[0]
+        if segments is None and independent:
+            segments = ops.batch_segments(B, 1, samples.device)
+        if self.args.tf_rcnn and B > 1 and segments is not None:
+            raise NotImplementedError('Transformer_RCNN with per-image RoI counts (independent or segmented detection)')
         fpn_out = self._fpn_nhwc(samples, lazy=True)
-        rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, independent=independent and segments is None,
-                                                                       segments=segments)
+        rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, segments=segments)
         return self.head.fast_rcnn.detect_device(fpn_out, rois, n_roi, nms_thresh, min_score)
 
     def forward(self, samples, nms_thresh=0.3, min_score=0.5):

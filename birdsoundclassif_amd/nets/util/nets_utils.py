@@ -84,10 +84,10 @@ def nms(bbox_pred, scores, nms_thresh=0.7, post_nms_topN=300, return_idx=False):
     bx = torch.zeros((B, cap, 4), device=dev, dtype=torch.float32)
     sc = torch.zeros((B, cap), device=dev, dtype=torch.float32)
     bx[:, :N], sc[:, :N] = bbox_pred.to(dev), scores.to(dev)
-    n_in = torch.full((1,), N, device=dev, dtype=torch.int32)
+    n_in = torch.full((B,), N, device=dev, dtype=torch.int32)
     post = min(int(post_nms_topN), cap)
     rois, rs, n_out = ops.nms_batched(bx, sc, n_in, nms_thresh, post)
-    n = int(n_out.item())
+    n = int(n_out[0].item())
     out = (rois[:, :n].to(bbox_pred.device), rs[:, :n].to(bbox_pred.device))
     if return_idx:
         # keep lists are recovered from the workspace-free outputs by matching positions (order preserving)

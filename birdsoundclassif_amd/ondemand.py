@@ -909,7 +909,7 @@ def lazy_pending(fm):
 
 def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
     """Compute the tiles of the deferred map `fm` under the windows of the RoIs assigned to `level` (the windows
-    `roi_pool` reads).  rois [B,cap,4], n_roi device int32[1] (or [B]: per-image counts), fmap_hw: (h, w) of every pyramid
+    `roi_pool` reads).  rois [B,cap,4], n_roi device int32 [B] (or [1]: `ops.roi_counts`), fmap_hw: (h, w) of every pyramid
     level.  No-op for a map that is not deferred.  May be called any number of times on the same map (each RoI pooling calls it
     with its own RoIs): the operands live as long as the map."""
     hit = _LAZY.get(fm.data_ptr())
@@ -927,7 +927,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
     img_bytes = H * W * U.shape[1] * 4
     cap = rois.shape[1]
     _chk(rois, name='rois')
-    per = ops.per_image_counts(n_roi, B)
+    n_roi = ops.roi_counts(n_roi, B)
     nl = len(fmap_hw)
     fh = (C.c_int * nl)(*[int(h) for h, _ in fmap_hw])
     fw = (C.c_int * nl)(*[int(w) for _, w in fmap_hw])
@@ -936,7 +936,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
     per_chunk = []
     for b0, nb, _ in st.chunks:
         key = (str(x.device), nb * blocks_per_img * 128, ops.LANE)
-        nr = n_roi[b0:b0 + nb] if per else n_roi
+        nr = n_roi[b0:b0 + nb]
         if keep:                                  # the backward pass reads the list again: a buffer of its own
             tiles = torch.empty((key[1],), device=x.device, dtype=torch.int32)
             n_blocks = torch.zeros((1,), device=x.device, dtype=torch.int32)
@@ -947,7 +947,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
                                             torch.zeros((1,), device=x.device, dtype=torch.int32))
             tiles, n_blocks = buf
         check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, _ptr(st.skip), 0, _ptr(tiles),
-                                  _ptr(n_blocks), per, _stream()), 'nbm_roi_tiles')
+                                  _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
         if st.lateral is not None:                # the input patches of these tiles first (16 pixels per listed tile)
             lt = st.lateral
             gemm_conv(lt.t[b0:b0 + nb], lt.wk, x[b0:b0 + nb], B=nb, H=H, W=W, Cin=lt.t.shape[-1], N=C_, w_ld=lt.wk.shape[1],
@@ -964,7 +964,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
                 tiles_d = torch.empty((key[1],), device=x.device, dtype=torch.int32)
                 nbd = torch.zeros((1,), device=x.device, dtype=torch.int32)
                 check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, None, 1, _ptr(tiles_d), _ptr(nbd),
-                                          per, _stream()), 'nbm_roi_tiles')
+                                          _stream()), 'nbm_roi_tiles')
                 host_d = _pinned_int()
                 host_d.copy_(nbd, non_blocking=True)
             ev = torch.cuda.Event()
@@ -1227,15 +1227,14 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
                             zero_note(pl, lambda p_=p_, c_=c_, nb_=nb, tl_=tl, n_=n: check(
                                 lib().nbm_zero_tiles(p_, nb_, H, W, c_, _ptr(tl_), n_, None, _stream()), 'nbm_zero_tiles'))
                 continue
-            per = ops.per_image_counts(n_roi, B)
             key = (str(g.device), nb * blocks_per_img * 128, ops.LANE)
             buf = _ROI_TILE_BUF.get(key)
             if buf is None:
                 buf = _ROI_TILE_BUF[key] = (torch.empty((key[1],), device=g.device, dtype=torch.int32),
                                             torch.zeros((1,), device=g.device, dtype=torch.int32))
             tiles, n_blocks = buf
-            check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(n_roi[b0:b0 + nb] if per else n_roi), nb, rois.shape[1], nl, level,
-                                      fh, fw, None if cell else _ptr(pat.full), 1, _ptr(tiles), _ptr(n_blocks), per, _stream()), 'nbm_roi_tiles')
+            check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(n_roi[b0:b0 + nb]), nb, rois.shape[1], nl, level,
+                                      fh, fw, None if cell else _ptr(pat.full), 1, _ptr(tiles), _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
             # composed reader: g holds the RoI pooling's share only (pattern pixels included), ADDED to the cell patches
             _wino23_tiles_run(g[b0:b0 + nb], Ut, None, gx.data_ptr() + b0 * img_bytes, tiles, n_blocks, None, 'wino23-dgrad-rois',
                               skip_pattern=st.stride if (overlap and comp is None) else 0, accumulate=overlap or comp is not None)

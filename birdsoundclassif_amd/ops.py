@@ -713,20 +713,9 @@ def anchor_targets(anchors, gt, n_gt, neg_t, pos_t):
     return lab, amx, flag
 
 
-def per_image_counts(n, B):
-    """Count tensors are int32 [1] (one count for the whole batch: the reference's batch-coupled semantics) or int32 [B] (every
-    image a batch of its own, `independent` detection) -> the `per_image` flag of the C ABI."""
-    if n.numel() == 1:
-        return 0
-    if n.numel() != B:
-        raise ValueError(f'count tensor with {n.numel()} entries for a batch of {B}')
-    return 1
-
-
 def segment_table(sizes, device='cuda'):
-    """Segment sizes (contiguous, in batch order) -> the int32 [2, B] table of nbm_rpn_select_seg / nbm_nms_batched_seg:
-    row 0 the first image of each image's segment, row 1 the segment's image count (on `device`; 'cpu' for a pinned staging
-    copy)."""
+    """Segment sizes (contiguous, in batch order) -> the int32 [2, B] table of nbm_rpn_select / nbm_nms_batched: row 0 the
+    first image of each image's segment, row 1 the segment's image count (on `device`; 'cpu' for a pinned staging copy)."""
     first, count = [], []
     b = 0
     for n in sizes:
@@ -740,61 +729,91 @@ def segment_table(sizes, device='cuda'):
     return t if device == 'cpu' else t.to(device)
 
 
+_BATCH_SEGMENTS = {}
+
+
+def batch_segments(B, size=None, device='cuda'):
+    """Read-only device table (`segment_table`) of B images in contiguous segments of `size` images each: None = the whole
+    batch is one segment (the reference's coupling for one model call on it), 1 = every image a model call of its own.
+    Cached per (device, B, size) and never evicted, because captured graphs hold these addresses.  A missing table is filled
+    by a blocking copy, so it is on the device before any stream reads it; that copy cannot happen during a graph capture
+    (the capture's warm-up steps fill the cache)."""
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    size = B if size is None else int(size)
+    key = (dev, B, size)
+    t = _BATCH_SEGMENTS.get(key)
+    if t is None:
+        if size <= 0 or B % size:
+            raise ValueError(f'a batch of {B} does not split into segments of {size}')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f'the segment table for a batch of {B} in segments of {size} would be created during a graph capture '
+                               '(the warm-up steps of the capture must run the same batch and coupling)')
+        t = _BATCH_SEGMENTS[key] = segment_table([size] * (B // size), dev)
+    return t
+
+
 def _chk_segments(segments, B):
     _chk(segments, torch.int32, 'segments')
     if tuple(segments.shape) != (2, B):
         raise ValueError(f'segment table of shape {tuple(segments.shape)} for a batch of {B}: expected (2, {B})')
+    return segments
 
 
-def rpn_select(boxes, keys, keep_count, top_n, fail_below, cap, per_image=False, segments=None):
-    """`segments` (int32 [2, B] on the device, `segment_table`): the counts are coupled within each segment only and come
-    back per image, n_sel int32 [B] (nbm_rpn_select_seg)."""
+def _chk_counts(n, B, name):
+    _chk(n, torch.int32, name)
+    if n.numel() != B:
+        raise ValueError(f'{name}: one count per image, got {n.numel()} for a batch of {B}')
+    return n
+
+
+def roi_counts(n, B, name='n_roi'):
+    """RoI counts of the RoI stages -> int32 [B], one count per image.  A single count is the same count for every image
+    (RoI tensors of R real rows per image); it is broadcast here, so the kernels always read n[b]."""
+    _chk(n, torch.int32, name)
+    if n.numel() == 1 and B > 1:
+        return n.expand(B).contiguous()
+    return _chk_counts(n, B, name)
+
+
+def rpn_select(boxes, keys, keep_count, top_n, fail_below, cap, segments=None):
+    """-> sel_boxes [B,cap,4], sel_scores [B,cap], n_sel int32 [B].  The counts are coupled within each segment of `segments`
+    (int32 [2, B] on the device, `segment_table`; None: `batch_segments(B)`, the whole batch)."""
     B, KA = keys.shape
+    _chk_counts(keep_count, B, 'keep_count')
+    segments = batch_segments(B, device=boxes.device) if segments is None else _chk_segments(segments, B)
     sel_boxes = torch.empty((B, cap, 4), device=boxes.device, dtype=torch.float32)
     sel_scores = torch.empty((B, cap), device=boxes.device, dtype=torch.float32)
-    if segments is not None:
-        _chk_segments(segments, B)
-        n_sel = torch.empty((B,), device=boxes.device, dtype=torch.int32)
-        check(lib().nbm_rpn_select_seg(_ptr(boxes), _ptr(keys), _ptr(keep_count), B, KA, top_n, fail_below, cap,
-                                       _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), _ptr(segments), _stream()),
-              'nbm_rpn_select_seg')
-        return sel_boxes, sel_scores, n_sel
-    n_sel = torch.empty((B if per_image and B > 1 else 1,), device=boxes.device, dtype=torch.int32)
+    n_sel = torch.empty((B,), device=boxes.device, dtype=torch.int32)
     check(lib().nbm_rpn_select(_ptr(boxes), _ptr(keys), _ptr(keep_count), B, KA, top_n, fail_below, cap,
-                               _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), per_image_counts(n_sel, B), _stream()), 'nbm_rpn_select')
+                               _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), _ptr(segments), _stream()), 'nbm_rpn_select')
     return sel_boxes, sel_scores, n_sel
 
 
 def nms_batched(boxes, scores, n_in, thresh, post_n, segments=None):
-    """boxes [B,cap,4] in walk order, n_in device int -> rois [B,post_n,4], scores [B,post_n], n_out device int.
-    `segments` (see rpn_select): n_in is int32 [B], the post-NMS truncation is coupled per segment, n_out int32 [B]."""
+    """boxes [B,cap,4] in walk order, n_in int32 [B] -> rois [B,post_n,4], scores [B,post_n], n_out int32 [B].  The post-NMS
+    truncation is coupled within each segment (see rpn_select)."""
     _chk(boxes, name='boxes'), _chk(scores, name='scores')
     B, cap = scores.shape
+    _chk_counts(n_in, B, 'n_in')
+    segments = batch_segments(B, device=boxes.device) if segments is None else _chk_segments(segments, B)
     words = cap // 64
     mask_ws = torch.empty((B * cap * words,), device=boxes.device, dtype=torch.int64)
     keep_ws = torch.empty((B * (cap + 1),), device=boxes.device, dtype=torch.int32)
     rois = torch.empty((B, post_n, 4), device=boxes.device, dtype=torch.float32)
     rs = torch.empty((B, post_n), device=boxes.device, dtype=torch.float32)
-    if segments is not None:
-        _chk_segments(segments, B)
-        _chk(n_in, torch.int32, 'n_in')
-        if n_in.numel() != B:
-            raise ValueError(f'segment-coupled NMS needs one count per image, got {n_in.numel()} for a batch of {B}')
-        n_out = torch.empty((B,), device=boxes.device, dtype=torch.int32)
-        check(lib().nbm_nms_batched_seg(_ptr(boxes), _ptr(scores), _ptr(n_in), B, cap, float(thresh), post_n, _ptr(mask_ws),
-                                        _ptr(keep_ws), _ptr(rois), _ptr(rs), _ptr(n_out), _ptr(segments), _stream()),
-              'nbm_nms_batched_seg')
-        return rois, rs, n_out
-    per = per_image_counts(n_in, B)
-    n_out = torch.empty((B if per else 1,), device=boxes.device, dtype=torch.int32)
+    n_out = torch.empty((B,), device=boxes.device, dtype=torch.int32)
     check(lib().nbm_nms_batched(_ptr(boxes), _ptr(scores), _ptr(n_in), B, cap, float(thresh), post_n, _ptr(mask_ws),
-                                _ptr(keep_ws), _ptr(rois), _ptr(rs), _ptr(n_out), per, _stream()), 'nbm_nms_batched')
+                                _ptr(keep_ws), _ptr(rois), _ptr(rs), _ptr(n_out), _ptr(segments), _stream()), 'nbm_nms_batched')
     return rois, rs, n_out
 
 
 def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w):
-    """fmaps: list of NHWC [B,h,w,C]; rois [B,cap,4]; n_roi device int32[1] -> pool, pe [B*cap,2,2,C], level [B,cap]."""
+    """fmaps: list of NHWC [B,h,w,C]; rois [B,cap,4]; n_roi device int32 [B] (or [1], `roi_counts`) -> pool,
+    pe [B*cap,2,2,C], level [B,cap]."""
     B, cap = rois.shape[:2]
+    n_roi = roi_counts(n_roi, B)
     C_ = fmaps[0].shape[-1]
     d = RoiDesc()
     for i, f in enumerate(fmaps):
@@ -803,7 +822,6 @@ def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w):
         d.fh[i], d.fw[i] = f.shape[1], f.shape[2]
     d.n_levels, d.C = len(fmaps), C_
     d.rois, d.n_roi, d.B, d.roi_cap = _chk(rois).data_ptr(), n_roi.data_ptr(), B, cap
-    d.n_roi_per_image = per_image_counts(n_roi, B)
     d.pe_f, d.pe_t, d.img_h, d.img_w = _chk(pe_f).data_ptr(), _chk(pe_t).data_ptr(), img_h, img_w
     pool = torch.zeros((B * cap, 2, 2, C_), device=rois.device, dtype=torch.float32)
     pe = torch.zeros((B * cap, 2, 2, C_), device=rois.device, dtype=torch.float32)
@@ -814,14 +832,16 @@ def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w):
 
 
 def rcnn_post(rois, n_roi, bbox_reg, bbox_cls, img_w, img_h, nms_thresh, min_score, proposal_number):
-    """-> det [B,cap,6] rows {class,x1,y1,x2,y2,score} sorted by (class, score desc), n_det [B]."""
+    """n_roi int32 [B] (or [1], `roi_counts`) -> det [B,cap,6] rows {class,x1,y1,x2,y2,score} sorted by
+    (class, score desc), n_det [B]."""
     B, cap = rois.shape[:2]
+    n_roi = roi_counts(n_roi, B)
     n_cls1 = bbox_cls.shape[-1]
     det = torch.zeros((B, cap, 6), device=rois.device, dtype=torch.float32)
     n_det = torch.zeros((B,), device=rois.device, dtype=torch.int32)
     check(lib().nbm_rcnn_post(_ptr(_chk(rois)), _ptr(n_roi), B, cap, _ptr(_chk(bbox_reg)), _ptr(_chk(bbox_cls)),
                               n_cls1, img_w, img_h, float(nms_thresh), float(min_score), int(proposal_number),
-                              _ptr(det), _ptr(n_det), per_image_counts(n_roi, B), _stream()), 'nbm_rcnn_post')
+                              _ptr(det), _ptr(n_det), _stream()), 'nbm_rcnn_post')
     return det, n_det
 
 

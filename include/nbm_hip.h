@@ -159,7 +159,7 @@ int nbm_wino23_conv_fused(const float* R, const float* U, const float* scale, co
  *   nbm_wino23_rows_tiles:       row half of the input transform for the four columns of every listed tile;
  *   nbm_wino23_conv_fused_tiles: as nbm_wino23_conv_fused, writes ONLY the pixels of the listed tiles;
  *   nbm_roi_tiles:               builds such a list on the device from the RoI windows (exactly the windows nbm_roi_pool
- *                                reads) of pyramid level `level`, without the tiles flagged in skip [TH * TW] (optional);
+ *                                reads; n_roi: device int32 [B], one count per image) of pyramid level `level`, without the tiles flagged in skip [TH * TW] (optional);
  *                                dilate > 0: the tiles within `dilate` pixels of a window instead (where the data gradient of
  *                                a 3x3 convolution of those windows is non-zero);
  *                                tiles must hold B * ceil(TH * TW / 128) * 128 entries; writes *n_blocks. */
@@ -175,8 +175,7 @@ int nbm_wino23_conv_fused_tiles(const float* R, const float* U, const float* sca
                                 int B, int H, int W, int C, int N, float* y, const int* tiles, int n_entries,
                                 const int* n_blocks, const unsigned* blk_info, void* stream);
 int nbm_roi_tiles(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level, const int* fh,
-                  const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks,
-                  int per_image /* n_roi[b] instead of n_roi[0]: see nbm_rpn_select */, void* stream);
+                  const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks, void* stream);
 /* Weight gradient of such a demand-driven convolution: the gradient wrt its output is zero outside the tiles that were
  * read, so only those tiles enter dU[xi] = dM[xi]^T V[xi].  F(2x2,3x3) transforms of the listed tiles (entry -1 = a zero
  * row) into COMPACT operands V [16][n_list][C] and dM [16][n_list][N] (+ bias gradient [N], optional, accumulated); the 16
@@ -390,64 +389,52 @@ int nbm_rpn_decode(const float* cls, const float* reg, const float* anchors /*[K
                    int n_anchor /*A: anchors per location*/, int img_w, int img_h, int min_size, float* boxes,
                    uint32_t* keys, int* keep_count, void* stream);
 
-/* Top-N selection by (score desc, index asc) among kept anchors, N = min(top_n, min_b keep_count[b]);
- * writes sel_boxes[b][cap][4], sel_scores[b][cap], n_sel[0] = N (0 if N < fail_below: "RPN failed"
- * layers.py:287-290).  -- layers.py:292-297.  cap >= top_n, cap power of two <= 4096.
- * per_image != 0: the B images are B independent batches of one (bulk inference over files that the reference CLI
- * runs one per model call, nbm_detect.py:24-28): N_b = min(top_n, keep_count[b]), n_sel[b] = N_b -- no image's
- * proposal count depends on its launch-mates.  The same flag on nbm_nms_batched / nbm_roi_pool (desc field) /
- * nbm_roi_tiles / nbm_rcnn_post makes them read their count as n[b] instead of n[0]. */
+/* Proposal counts.  Every count pointer of this section (n_sel, n_in, n_out, n_roi) is a device int32 [B], one count
+ * per image.  How the images are coupled is decided by the segment table `seg` of the two entry points below, a device
+ * int32 [2][B]: seg[b] = first image of b's segment, seg[B + b] = its image count.  Each contiguous segment is one model
+ * call of the reference: the pre- and post-NMS top-N (layers.py:287, nets_utils.py:236) and the "RPN failed" rule are
+ * minima over that segment alone.  One segment of B images is the reference's single call on the batch; B segments of
+ * one image are B independent calls (bulk inference over files that the reference CLI runs one per model call,
+ * nbm_detect.py:24-28; windows [k*bs, (k+1)*bs) of one file, run_detection.py:40-67, form one segment each).
+ * seg == NULL returns NBM_EINVAL. */
+
+/* Top-N selection by (score desc, index asc) among kept anchors, N_b = min(top_n, min over b's segment of
+ * keep_count); N_b = 0 if < fail_below ("RPN failed", layers.py:287-290).  Writes sel_boxes[b][cap][4],
+ * sel_scores[b][cap], n_sel[b] = N_b.  -- layers.py:292-297.  cap >= top_n, cap power of two <= 4096. */
 int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
                    int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel,
-                   int per_image, void* stream);
+                   const int* seg, void* stream);
 
-/* nbm_rpn_select with SEGMENT coupling: the batch is cut into contiguous segments, each one model call of the reference
- * (run_detection.py:40-67: windows [k*bs, (k+1)*bs) of one file).  seg: device int32 [2][B], seg[b] = first image of b's
- * segment, seg[B + b] = its image count.  N_b = min(top_n, min over b's segment of keep_count), 0 if < fail_below;
- * n_sel[b] = N_b.  Segments never couple with each other; all-singleton segments give per_image. */
-int nbm_rpn_select_seg(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
-                       int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel,
-                       const int* seg, void* stream);
-
-/* Greedy NMS in the given order (suppress IoU >= thresh, +1 pixel convention) then the batch-coupled
- * truncation R = min(post_n, min_b #keep_b) -- nets_utils.py:189-245.  n_in[0] boxes per image.
+/* Greedy NMS in the given order (suppress IoU >= thresh, +1 pixel convention) of the n_in[b] boxes of image b, then
+ * the coupled truncation R_b = min(post_n, min over b's segment of #keep) -- nets_utils.py:189-245.
  * Workspaces: mask_ws B*cap*(cap/64) uint64, keep_ws B*(cap+1) int32.  Writes rois[b][post_n][4],
- * roi_scores[b][post_n], n_out[0] = R.  cap: multiple of 64, <= 4096.
- * per_image != 0: n_in[b] boxes in image b, R_b = min(post_n, #keep_b), n_out[b] = R_b. */
+ * roi_scores[b][post_n], n_out[b] = R_b.  cap: multiple of 64, <= 4096. */
 int nbm_nms_batched(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh,
                     int post_n, uint64_t* mask_ws, int* keep_ws, float* rois, float* roi_scores, int* n_out,
-                    int per_image, void* stream);
-
-/* nbm_nms_batched with SEGMENT coupling (seg as in nbm_rpn_select_seg): n_in[b] boxes in image b,
- * R_b = min(post_n, min over b's segment of #keep), n_out[b] = R_b. */
-int nbm_nms_batched_seg(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh,
-                        int post_n, uint64_t* mask_ws, int* keep_ws, float* rois, float* roi_scores, int* n_out,
-                        const int* seg, void* stream);
+                    const int* seg, void* stream);
 
 /* ROIPooling (layers.py:406-497): level assignment, window, 2x2 adaptive average of the FPN map and of
  * the separable positional encoding.  fmaps: 5 device pointers (NHWC, C channels); pe_f [img_h][C/2],
- * pe_t [img_w][C/2].  n_roi[0] RoIs per image out of roi_cap slots.  Outputs NHWC [B*roi_cap][2][2][C]. */
+ * pe_t [img_w][C/2].  n_roi[b] RoIs in image b out of roi_cap slots.  Outputs NHWC [B*roi_cap][2][2][C]. */
 typedef struct nbm_roi_desc {
   const float* fmap[5];
   int fh[5], fw[5];
   int n_levels, C;
   const float* rois;     /* [B][roi_cap][4] */
-  const int* n_roi;      /* device scalar, or [B] with n_roi_per_image */
+  const int* n_roi;      /* device int32 [B] */
   int B, roi_cap;
   const float* pe_f; const float* pe_t; int img_h, img_w;
   float* pool; float* pe; int* level;
-  int n_roi_per_image;   /* != 0: n_roi[b] RoIs in image b (see nbm_rpn_select) */
 } nbm_roi_desc;
 int nbm_roi_pool(const nbm_roi_desc* d, void* stream);
 
-/* FastRCNN eval post-processing (layers.py:688-776) for B images, n_roi[0] RoIs each:
+/* FastRCNN eval post-processing (layers.py:688-776) for B images, n_roi[b] RoIs in image b:
  * class arg-max, per-class delta gather, decode+clip, sort by score, drop background, class-agnostic
  * NMS, per-class NMS (top proposal_number) and score > min_score.  Output rows sorted by (class asc,
  * score desc): det[b][cap][6] = {class, x1, y1, x2, y2, score}, n_det[b]. */
 int nbm_rcnn_post(const float* rois, const int* n_roi, int B, int roi_cap, const float* bbox_reg,
                   const float* bbox_cls, int n_cls1 /*1+num_classes*/, int img_w, int img_h,
-                  float nms_thresh, float min_score, int proposal_number, float* det, int* n_det,
-                  int per_image /* n_roi[b] */, void* stream);
+                  float nms_thresh, float min_score, int proposal_number, float* det, int* n_det, void* stream);
 
 /* Per-file merge of the window outputs of one recording (run_detection.py:163-249), for any box count up to
  * NBM_MERGE_MAX_N.  nbm_merge_collect -> nbm_merge_nms -> nbm_merge_gather, all on one stream, no host sync. */

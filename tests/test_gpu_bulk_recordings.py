@@ -1,5 +1,5 @@
-"""GPU: the recording route (bulk.detect_recordings) -- segment-coupled proposal counts (nbm_rpn_select_seg /
-nbm_nms_batched_seg) against the coupled entry points on each segment alone, NbmModel.detect(segments=...) against one call
+"""GPU: the recording route (bulk.detect_recordings) -- segment-coupled proposal counts (nbm_rpn_select /
+nbm_nms_batched with a segment table) against one call on each segment alone, NbmModel.detect(segments=...) against one call
 per segment, the window-table front end (nbm_spec_windows_table) against nbm_spec_windows, replays of the captured graph, and
 the CLI on a mixed shard byte for byte against the per-file driver."""
 import ast
@@ -79,21 +79,22 @@ def test_segment_below_fail_threshold_fails_alone():
     assert (n_sel[:5] >= fail).all() and (n_sel[8:] >= fail).all() and (n_out[:5] > 0).all() and (n_out[8:] > 0).all()
 
 
-def test_singleton_segments_equal_per_image():
+def test_singleton_segments_equal_one_image_per_call():
     a = default_args(device='cuda')
     B = 9
     boxes, keys, cnt = _proposal_inputs(B, 99, starved=[(3, 5)])
     pre, post, fail = a.pre_nms_topN_eval, a.post_nms_topN_eval, a.rcnn_batch_size
     cap = 1 << (pre - 1).bit_length()
     seg = ops.segment_table([1] * B)
-    got = ops.rpn_select(boxes, keys, cnt, pre, fail, cap, segments=seg)
-    ref = ops.rpn_select(boxes, keys, cnt, pre, fail, cap, per_image=True)
-    for x, y in zip(got, ref):
-        assert torch.equal(x, y)
-    got = ops.nms_batched(*got, a.nms_thresh, post, segments=seg)
-    ref = ops.nms_batched(*ref, a.nms_thresh, post)
-    for x, y in zip(got, ref):
-        assert torch.equal(x, y)
+    sel = ops.rpn_select(boxes, keys, cnt, pre, fail, cap, segments=seg)
+    got = ops.nms_batched(*sel, a.nms_thresh, post, segments=seg)
+    for b in range(B):                                       # reference: B calls of one image each
+        sl = slice(b, b + 1)
+        sel1 = ops.rpn_select(boxes[sl].contiguous(), keys[sl].contiguous(), cnt[sl].contiguous(), pre, fail, cap)
+        for x, y in zip(sel, sel1):
+            assert torch.equal(x[sl], y)
+        for x, y in zip(got, ops.nms_batched(*sel1, a.nms_thresh, post)):
+            assert torch.equal(x[sl], y)
     assert got[2][3].item() == 0 and (got[2] > 0).sum().item() == B - 1
 
 

@@ -256,6 +256,21 @@ def test_transformer_rcnn_head_vs_reference_golden(tag, pe_qk):
         assert np.array_equal(rows2[:, :6], g[f'{tag}.dets_min0.2'][:, :6])
 
 
+def test_transformer_rcnn_refuses_independent_images():
+    """The transformer head attends over one RoI count for the whole batch: independent detection of B > 1 images is refused,
+    B = 1 is one model call and runs."""
+    from birdsoundclassif_amd.nets import build_model
+    from birdsoundclassif_amd.train import default_args
+    m, _ = build_model(default_args(device='cuda', tf_rcnn=True))
+    m.load_state_dict(filler_state_dict(tf_rcnn=True))
+    m = m.cuda().eval()
+    x = torch.from_numpy(synth.image_batch(0, 2))[:, None].cuda()
+    with pytest.raises(NotImplementedError):
+        m.detect(x, 0.3, 0.2, independent=True)
+    det, n_det = m.detect(x[:1], 0.3, 0.2, independent=True)
+    assert det.shape[0] == 1 and n_det.shape == (1,)
+
+
 def test_mha_small_masks_padded_keys():
     """nbm_mha_small against torch on both token layouts, with a device-side valid-length counter."""
     from birdsoundclassif_amd import ops

@@ -229,8 +229,8 @@ def test_rpn_failed_path():
     assert rois.numel() == 0 and scores.numel() == 0
 
 
-def test_proposal_layer_independent_images_equal_one_image_per_call():
-    """`independent=True` (bulk inference): every image of the launch gets the RoIs the reference gives it when it is run ALONE
+def test_proposal_layer_singleton_segments_equal_one_image_per_call():
+    """Singleton segments (bulk inference, `independent=True`): every image of the launch gets the RoIs the reference gives it when it is run ALONE
     (one file per model call, reference nbm_detect.py:24-28) -- the batch-coupled minima of layers.py:287 / nets_utils.py:236 do
     not leak between launch-mates.  Image 1 keeps few anchors, image 2 fails ("RPN failed"), images 0 and 3 fill the top-N."""
     from birdsoundclassif_amd.nets.layers import ProposalLayer
@@ -242,11 +242,11 @@ def test_proposal_layer_independent_images_equal_one_image_per_call():
     reg[2] = -20.0                                  # image 2: none survives
     pl = ProposalLayer(default_args(), 5).eval()
     rois, scores, n = pl.forward_device(cls.permute(0, 2, 3, 1).contiguous().cuda(), reg.permute(0, 2, 3, 1).contiguous().cuda(),
-                                        independent=True)
+                                        segments=ops.batch_segments(4, 1))
     assert n.shape == (4,)
     n = n.cpu().tolist()
     coupled = pl.forward_device(cls.permute(0, 2, 3, 1).contiguous().cuda(), reg.permute(0, 2, 3, 1).contiguous().cuda())[2]
-    assert int(coupled.item()) == 0                 # one call on the whole batch: image 2 fails everybody (reference semantics)
+    assert coupled.tolist() == [0] * 4              # one call on the whole batch: image 2 fails everybody (reference semantics)
     seen = set()
     for b in range(4):
         ref_rois, ref_scores = O.proposal_layer(cfg, cls[b:b + 1], reg[b:b + 1], training=False)
@@ -259,7 +259,7 @@ def test_proposal_layer_independent_images_equal_one_image_per_call():
     assert 0 in seen and 50 in seen and len(seen) >= 3, seen
 
 
-def test_nms_ties_and_order():
+def test_nms_ties_and_order_in_every_image():
     # many identical boxes / scores: greedy NMS must walk in the given order
     boxes = torch.tensor([[10., 10, 50, 50], [10, 10, 50, 50], [12, 12, 52, 52], [200, 100, 260, 160],
                           [201, 101, 261, 161], [500, 300, 600, 370]])[None].repeat(2, 1, 1)
@@ -269,10 +269,10 @@ def test_nms_ties_and_order():
     bx = torch.zeros(2, 64, 4)
     sc = torch.zeros(2, 64)
     bx[:, :6], sc[:, :6] = boxes, scores
-    n_in = torch.tensor([6], dtype=torch.int32).cuda()
+    n_in = torch.tensor([6, 6], dtype=torch.int32).cuda()
     rois, rs, n_out = ops.nms_batched(bx.cuda(), sc.cuda(), n_in, 0.3, 50)
-    n = int(n_out.item())
-    assert n == ref_b.shape[1]
+    assert n_out.tolist() == [ref_b.shape[1]] * 2
+    n = ref_b.shape[1]
     assert torch.equal(rois[:, :n].cpu(), ref_b) and torch.equal(rs[:, :n].cpu(), ref_s)
 
 

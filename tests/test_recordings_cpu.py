@@ -1,5 +1,6 @@
 """CPU: the host side of the recording route (bulk.detect_recordings) -- the segment packer, the segment table, the window count
 from a wav header, which files the route takes, and the C ABI entries it binds."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -90,9 +91,11 @@ def test_recording_files_takes_mono_pcm16_recordings_only(tmp_path):
     assert sorted(os.path.basename(f) for f in rest) == ['junk.wav', 'odd_rate.wav', 'stereo.wav']
 
 
-def test_new_entry_points_are_bound():
-    for name in ('nbm_rpn_select_seg', 'nbm_nms_batched_seg', 'nbm_spec_windows_table'):
-        assert name in _lib.SIGNATURES
-    assert _lib.SIGNATURES['nbm_rpn_select_seg'][:-2] == _lib.SIGNATURES['nbm_rpn_select'][:-2]
-    assert _lib.SIGNATURES['nbm_nms_batched_seg'][:-2] == _lib.SIGNATURES['nbm_nms_batched'][:-2]
+def test_proposal_entry_points_take_a_segment_table():
+    assert 'nbm_spec_windows_table' in _lib.SIGNATURES
+    # one proposal-count mode: the segment table is a required argument of the two proposal entry points
+    for name in ('nbm_rpn_select_seg', 'nbm_nms_batched_seg'):
+        assert name not in _lib.SIGNATURES
+    for name in ('nbm_rpn_select', 'nbm_nms_batched'):
+        assert _lib.SIGNATURES[name][-2:] == [C.c_void_p, C.c_void_p]          # (pointer seg, pointer stream)
     assert ops.WINDOW_ENTRY_WORDS * 8 == 40          # sizeof(struct nbm_window_entry)
