@@ -8,7 +8,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# NBM_LIB: another build of the same ABI (scripts/wino_fused_probe.py uses the -DNBM_ABLATE build, `make -C csrc ablate`)
+# NBM_LIB: load another build of the same ABI instead of the one in this directory
 LIB_PATH = os.environ.get('NBM_LIB') or os.path.join(_HERE, 'libnbm_hip.so')
 CSRC = os.path.join(_HERE, 'csrc')
 

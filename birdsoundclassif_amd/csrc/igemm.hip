@@ -552,23 +552,20 @@ extern "C" int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream) {
   // An output width 64 past a multiple of 128 (the cell-domain data-gradient planes of the deferred lateral: 256 -> 448): the last 128-wide
   // tile would be half padding -- the first N - 64 channels on 128-wide tiles, the last 64 on the 64-wide kernel.  Every output element is the
   // same sum in the same order either way (round 5; weight-gradient twin: nbm_conv_wgrad).
-  {
-    static const int tail_split = getenv("NBM_NT_TAIL") ? atoi(getenv("NBM_NT_TAIL")) : 1;
-    if (tail_split && d->N > 128 && (d->N & 127) == 64 && !d->rows && !d->up && !d->bits_out && !d->shift_per_row && (d->Cin % BK) == 0 &&
-        d->kh * d->kw * d->Cin > 256) {
-      nbm_gemm_desc a = *d, b = *d;
-      const int n0 = d->N - 64;
-      a.N = n0;
-      b.N = 64;
-      b.w = d->w + (long long)n0 * d->w_ld;
-      b.y = d->y + n0;
-      if (d->scale) b.scale = d->scale + n0;
-      if (d->shift) b.shift = d->shift + n0;
-      if (d->residual) b.residual = d->residual + n0;
-      if (d->mask) b.mask = d->mask + n0;
-      const int rc = nbm_gemm_conv(&a, stream);
-      return rc ? rc : nbm_gemm_conv(&b, stream);
-    }
+  if (d->N > 128 && (d->N & 127) == 64 && !d->rows && !d->up && !d->bits_out && !d->shift_per_row && (d->Cin % BK) == 0 &&
+      d->kh * d->kw * d->Cin > 256) {
+    nbm_gemm_desc a = *d, b = *d;
+    const int n0 = d->N - 64;
+    a.N = n0;
+    b.N = 64;
+    b.w = d->w + (long long)n0 * d->w_ld;
+    b.y = d->y + n0;
+    if (d->scale) b.scale = d->scale + n0;
+    if (d->shift) b.shift = d->shift + n0;
+    if (d->residual) b.residual = d->residual + n0;
+    if (d->mask) b.mask = d->mask + n0;
+    const int rc = nbm_gemm_conv(&a, stream);
+    return rc ? rc : nbm_gemm_conv(&b, stream);
   }
   IgemmParams p{};
   p.x = d->x; p.w = d->w; p.y = d->y; p.scale = d->scale; p.shift = d->shift; p.residual = d->residual;
@@ -629,9 +626,8 @@ extern "C" int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream) {
     if (k32 == 2 && nt == 8 && d->residual) return launch_stream<2, 8, 4, 8, 1>(sp, st);
     if (k32 == 2 && nt == 2) return launch_stream<2, 2, 2, 8, 2>(sp, st);
     if (k32 == 8 && nt == 2) return launch_stream<8, 2, 2, 8, 1>(sp, st);
-    // wider layers in slices of N (experiment switch NBM_STREAM_SLICED, default on)
-    static const int sliced = getenv("NBM_STREAM_SLICED") ? atoi(getenv("NBM_STREAM_SLICED")) : 1;
-    if (sliced && d->residual) {
+    // wider layers in slices of N
+    if (d->residual) {
       if (k32 == 4 && nt % 4 == 0 && nt <= 32) return launch_stream<4, 4, 4, 8, 1>(sp, st, nt / 4);      // 128 -> 512: 4 slices of 128
       if (k32 == 8 && nt % 2 == 0 && nt <= 64) return launch_stream<8, 2, 2, 8, 1>(sp, st, nt / 2);      // 256 -> 1024: 16 slices of 64
     }
@@ -642,20 +638,15 @@ extern "C" int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream) {
     // Read per call: the parity tests flip it inside one process.  The choice depends on the LAYER (K, N), never on the number of rows:
     // a clip's result must not depend on how many clips share its batch (the two kernels sum in different orders).
     const char* split_env = getenv("NBM_SPLIT_BF16");
-    static const int split_min_nk = getenv("NBM_SPLIT_MIN_NK") ? atoi(getenv("NBM_SPLIT_MIN_NK")) : 9;      // experiment switch (>= 3)
-    if (split_env && split_env[0] == '1' && fast && p.vec_epi && p.nk >= (split_min_nk < 3 ? 3 : split_min_nk) && d->kh * d->kw < 63)
+    if (split_env && split_env[0] == '1' && fast && p.vec_epi && p.nk >= 9 && d->kh * d->kw < 63)
       return nbm_igemm::split_launch(p, d->groups, st);
     // deep K: half-step LDS stages, three workgroups per CU (igemm_h16.hip: the same products in the same order as the two-stage kernel below,
-    // 2-14 % faster launch by launch at B = 64, scripts/h16_probe.py).  NBM_H16 = 0: the two-stage kernel; 3 (default) / 4: workgroups per CU;
-    // from NBM_H16_MIN_NK K-steps up (default 9: up to 8 the single-stage kernel below stays)
+    // 2-14 % faster launch by launch at B = 64, scripts/h16_probe.py).  NBM_H16 = 0: the two-stage kernel.  From 9 K-steps up; up to 8 the
+    // single-stage kernel below stays
     const char* h16_env = getenv("NBM_H16");                   // read per call: the parity test flips it inside one process
-    const int h16 = h16_env ? atoi(h16_env) : 3;
-    const char* h16_min_env = getenv("NBM_H16_MIN_NK");
-    const int h16_min = h16_min_env ? atoi(h16_min_env) : 9;
-    if (h16 && fast && p.vec_epi && p.nk >= h16_min && d->kh * d->kw < 63) return nbm_igemm::h16_launch(p, d->groups, h16, st);
+    if (!(h16_env && atoi(h16_env) == 0) && fast && p.vec_epi && p.nk >= 9 && d->kh * d->kw < 63) return nbm_igemm::h16_launch(p, d->groups, st);
     // short K and a 16-byte epilogue: the three-workgroups-per-CU variant (see the template comment)
-    static const int shortk_max = getenv("NBM_SHORTK_MAX") ? atoi(getenv("NBM_SHORTK_MAX")) : 8;   // 0 disables
-    if (fast && p.vec_epi && p.nk <= shortk_max)
+    if (fast && p.vec_epi && p.nk <= 8)
       return launch_s1(p, d->groups, st);
 
     return fast ? launch<128, 128, 64, 64, A_FAST, EPI_STD>(p, d->groups, st)
@@ -665,11 +656,10 @@ extern "C" int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream) {
     // (NEGATIVE, round 5: 256 x 64 tiles with a 64 x 64 patch per wave -- the fragment reuse of the 128 x 128 kernel -- on the layer1 3x3
     // 64 -> 64 @94x256: two LDS stages / one workgroup per CU 1.30 ms against 1.14 at B = 64, one stage / two workgroups per CU 1.15:
     // the 64-wide tile's time is not its LDS reads per MFMA)
-    // single LDS stage / three workgroups per CU for the 64-wide tile up to K = 32 * s1_n64 (NBM_S1_N64; 0 = never): this tile spends half the
+    // single LDS stage / three workgroups per CU for the 64-wide tile up to K = 32 * 20: this tile spends half the
     // MFMA cycles per K-step of the 128-wide one, so its prologue / epilogue weigh double and the third workgroup pays up to K = 576 (layer1's
     // 3x3 64 -> 64 @94x256: 1.075 -> 0.99 ms at B = 64, 2.05 -> 1.83 at B = 128; same K order, same bits)
-    static const int s1_n64 = getenv("NBM_S1_N64") ? atoi(getenv("NBM_S1_N64")) : 20;
-    if (fast && p.vec_epi && p.nk <= s1_n64) {
+    if (fast && p.vec_epi && p.nk <= 20) {
       dim3 grid(p.m_tiles * p.n_tiles, 1, d->groups);
       hipLaunchKernelGGL((igemm_kernel<128, 64, 64, 32, A_FAST, EPI_STD, 1>), grid, dim3(256), 0, st, p);
       return nbm_launch_status();

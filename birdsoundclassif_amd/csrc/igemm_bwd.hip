@@ -48,28 +48,11 @@ struct BwdParams {
   int phased;                // NN, stride 2: M tiles are grouped by the parity class of (iy + pad, ix + pad)
   int ph_tiles[4];           //   M tiles of each class; tile_m = 4 * (tile within class) + class, so the four classes of
                              //   one image region run side by side and fill the same DRAM pages together
-  int ablate;                // NN, timing-only build (-DNBM_ABLATE_NN, `make ablate_nn`; never shipped): NBM_NN_ABLATE bits, see ABL_*
   // NN: launch-invariant divisors of the row decode (nbm_fastdiv, nbm_common.h): pixels per image and row width of the (parity class's)
   // pixel grid, the stride, and the full grid again for the half-resolution residual
   nbm_fastdiv fd_hw[4], fd_w[4], fd_st, fd_HW, fd_W;
   nbm_fastdiv fd_howo, fd_wo;   // TN: output pixels per image, output row width
 };
-
-// Attribution of igemm_nn_kernel's time (scripts/dgrad_ablate.py -> profiles/r05_dgrad_attribution.txt).  Each bit
-// removes ONE component from the kernel; results are wrong by design.  The shipped build compiles none of this (`abl()` is constant 0).
-enum { ABL_NO_MASK = 1, ABL_NO_RESIDUAL = 2, ABL_NO_ASCALE = 4, /* 8: was the tap select -- unmasked taps read outside the tensor */ ABL_NO_STORE = 16, ABL_NO_EPILOGUE = 32,
-       ABL_NO_LOADS = 64, ABL_NO_LDS_WRITES = 128 };
-#ifdef NBM_ABLATE_NN
-#define NBM_ABL(p, bit) (((p).ablate & (bit)) != 0)
-// per parity class (0 when not phased): cycles in prologue / K loop / epilogue, tiles (thread 0 of every workgroup; clock64)
-__device__ unsigned long long nbm_nn_dbg[24];   // [class][address arithmetic | first loads + LDS write | K loop | epilogue], [16 + class] tiles; [20..23] weight-gradient kernel: prologue | K loop | epilogue (atomics) | tiles
-#define NBM_DBG_T(var) const long long var = clock64()
-#define NBM_DBG_ADD(slot, v) do { if (threadIdx.x == 0) atomicAdd(&nbm_nn_dbg[slot], (unsigned long long)(v)); } while (0)
-#else
-#define NBM_ABL(p, bit) false
-#define NBM_DBG_T(var)
-#define NBM_DBG_ADD(slot, v)
-#endif
 
 __device__ __forceinline__ int xcd_tile(int nwg, int bid) {
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
@@ -105,7 +88,6 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
   float* Bs = lds + STAGES * BM * AP;
   if constexpr (STAGES == 2) nbm_stagger_priority();
 
-  NBM_DBG_T(dbg_t0);
   const int wg = xcd_tile(gridDim.x, blockIdx.x);
   const int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   const int bm0 = tile_m * BM, bn0 = tile_n * BN;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
     a_rel[i] = ((unsigned)(base - blk_base) + koff) * 4u;
     // taps that reach this pixel: filter rows r with r = py (mod stride) whose G row fy - r / stride exists, likewise columns, then their
     // product -- selects only (as a kh x kw nest of data-dependent branches this was the longest part of the tile prologue: 28 k of the
-    // 37 k cycles in front of the first load of a 3x3 tile, cycle counters of the `ablate_nn` build, round 5)
+    // 37 k cycles in front of the first load of a 3x3 tile, cycle counters of a timing-only attribution build, round 5)
     unsigned long long mk = 0ull;
     unsigned rowm = 0u, colm = 0u;
     for (int r = 0; r < p.kh; ++r) {
@@ -208,10 +190,7 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
   f32x4 ra[AR], rb[BPASS], rsc = {1.f, 1.f, 1.f, 1.f};
   int cur_r = r_begin, cur_s = s_begin, cur_n0 = 0, cur_h = 0;
 
-  int abl_loads_done = 0;
   auto load_tiles = [&]() {
-    if (NBM_ABL(p, ABL_NO_LOADS) && abl_loads_done >= 2) return;           // operands stay what the first two loads fetched
-    ++abl_loads_done;
     const int tap = cur_r * p.kw + cur_s;
     const int n0h = cur_n0 + 8 * cur_h;                                    // (half-step: the second half starts 8 K values further)
     const unsigned a_soff = (unsigned)((maxoff - ((long long)divst(cur_r) * p.Wo + divst(cur_s)) * p.g_ld + n0h) * 4);
@@ -220,19 +199,16 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
     for (int i = 0; i < AR; ++i) ra[i] = buf_load4(rsrc_a, ((a_taps[i] >> tap) & 1ull) ? a_rel[i] : OOB, a_soff);
 #pragma unroll
     for (int i = 0; i < BPASS; ++i) rb[i] = buf_load4(rsrc_b, b_rel[i], b_soff);
-    if (p.a_scale && !NBM_ABL(p, ABL_NO_ASCALE)) rsc = *reinterpret_cast<const f32x4*>(p.a_scale + n0h + koff);
+    if (p.a_scale) rsc = *reinterpret_cast<const f32x4*>(p.a_scale + n0h + koff);
     if (HS && (cur_h ^= 1) != 0) return;                                   // the other half of the same (tap, 32-wide K) step comes next
     cur_s += t_step;
     if (cur_s >= p.kw) { cur_s = s_begin; cur_r += t_step; if (cur_r >= p.kh) { cur_r = r_begin; cur_n0 += BK; } }
   };
-  int abl_writes_done = 0;
   auto store_lds = [&](int buf) {
-    if (NBM_ABL(p, ABL_NO_LDS_WRITES) && abl_writes_done >= 2) return;
-    ++abl_writes_done;
 #pragma unroll
     for (int i = 0; i < AR; ++i) {
       f32x4 v = ra[i];
-      if (!NBM_ABL(p, ABL_NO_ASCALE)) { v[0] *= rsc[0]; v[1] *= rsc[1]; v[2] *= rsc[2]; v[3] *= rsc[3]; }
+      v[0] *= rsc[0]; v[1] *= rsc[1]; v[2] *= rsc[2]; v[3] *= rsc[3];
       *reinterpret_cast<f32x4*>(As + (buf * BM + r0 + ARPP * i) * AP + c4 * 4) = v;
     }
 #pragma unroll
@@ -269,7 +245,6 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
   const int n_r = r_begin < p.kh ? (p.kh - r_begin + t_step - 1) / t_step : 0;
   const int n_s = s_begin < p.kw ? (p.kw - s_begin + t_step - 1) / t_step : 0;
   const int nk = ((p.N + BK - 1) / BK) * n_r * n_s;          // 0: no tap reaches this parity class, dX = residual
-  NBM_DBG_T(dbg_t0b);
   const int n_st = HS ? 2 * nk : nk;                             // LDS stages of the K loop
   if constexpr (STAGES == 2) {
     if (n_st > 0) {
@@ -279,7 +254,6 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
     if (n_st > 1) load_tiles();
   }
 
-  NBM_DBG_T(dbg_t1);
   auto k_step = [&](int kt, auto store_c, auto load_c) {
     constexpr bool STORE = decltype(store_c)::value, LOAD = decltype(load_c)::value;
     const int cur = kt & 1;
@@ -338,28 +312,12 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
     }
   }
   __syncthreads();
-  NBM_DBG_T(dbg_t2);
-#ifdef NBM_ABLATE_NN
-  const int dbg_c = p.phased ? 4 * (tile_m & 3) : 0;
-  NBM_DBG_ADD(dbg_c, dbg_t0b - dbg_t0); NBM_DBG_ADD(dbg_c + 1, dbg_t1 - dbg_t0b); NBM_DBG_ADD(dbg_c + 2, dbg_t2 - dbg_t1); NBM_DBG_ADD(16 + dbg_c / 4, 1);
-#endif
 
   float* __restrict__ og = p.out + (long long)grp * p.out_gs;
-  const float* __restrict__ rg = (p.residual && !NBM_ABL(p, ABL_NO_RESIDUAL)) ? p.residual + (long long)grp * p.res_gs : nullptr;
-  const unsigned* __restrict__ mb_ = NBM_ABL(p, ABL_NO_MASK) ? nullptr : p.mask_bits;     // the mask as bits takes precedence
-  const float* __restrict__ mk_ = (NBM_ABL(p, ABL_NO_MASK) || mb_) ? nullptr : p.mask;
-  const float* __restrict__ r2_ = NBM_ABL(p, ABL_NO_RESIDUAL) ? nullptr : p.residual2;
-  if (NBM_ABL(p, ABL_NO_EPILOGUE)) {                                       // keep the accumulators alive: a store that never happens
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) t += acc[i][j][e];
-    if (t == 1.2345e-30f) og[0] = t;
-    return;
-  }
+  const float* __restrict__ rg = p.residual ? p.residual + (long long)grp * p.res_gs : nullptr;
+  const unsigned* __restrict__ mb_ = p.mask_bits;     // the mask as bits takes precedence
+  const float* __restrict__ mk_ = mb_ ? nullptr : p.mask;
+  const float* __restrict__ r2_ = p.residual2;
   auto out_pixel = [&](int q) -> long long {                  // output row of tile row q (q < rows_here)
     if (!p.phased) return q;
     int b, iy, ix;
@@ -448,13 +406,9 @@ __global__ __launch_bounds__(256, (STAGES == 1 || HS) ? 3 : 2) void igemm_nn_ker
 #pragma unroll
           for (int e = 0; e < 4; ++e) if (!((by >> (8 * e)) & 1u)) v[e] = 0.f;
         }
-        if (!NBM_ABL(p, ABL_NO_STORE) || v[0] == 1.2345e-30f) *reinterpret_cast<f32x4*>(og + (long long)m * p.out_ld + c) = v;
+        *reinterpret_cast<f32x4*>(og + (long long)m * p.out_ld + c) = v;
       }
     }
-#ifdef NBM_ABLATE_NN
-    __syncthreads();
-    NBM_DBG_ADD(dbg_c + 3, clock64() - dbg_t2);
-#endif
     return;
   }
 #pragma unroll
@@ -493,7 +447,7 @@ enum { B_SAME = 0, B_STRIDED = 1, B_GENERIC = 2 };
 
 // BM: rows of the dW tile = output channels n of the convolution.  128 by default; 64 for layers with N <= 64 (ResNet layer1:
 // with the 128-row tile half of every MFMA multiplied the zero padding of the G tile -- 59 TF/s "executed" on 3x3 64 -> 64).
-template <int BN, int BMODE, int SCHED = 0, int BM = 128>
+template <int BN, int BMODE, int BM = 128>
 __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
   constexpr int WM = BM / 2, WN = BN / 2, MT = WM / 32, NT = WN / 32;
   constexpr int AP = BM + 4, BP = BN + 4;
@@ -502,7 +456,6 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
   float* As = lds;                    // [2][32][AP]   G tile:  pixel-major, n contiguous
   float* Bs = lds + 2 * BK * AP;      // [2][32][BP]   X tile:  pixel-major, c contiguous
 
-  NBM_DBG_T(dbg_t0);
   const int wg = xcd_tile(gridDim.x, blockIdx.x);
   const int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   const int bm0 = tile_m * BM;                      // n0
@@ -683,34 +636,29 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
     mfma_group(Ab, Bb, 0);
     if constexpr (STORE) {
       store_lds(cur ^ 1);
-      if constexpr (SCHED != 2) {
-        __builtin_amdgcn_sched_group_barrier(0x100, (SCHED == 1 ? 2 : 4) * (MT + NT), 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 4 * (MT + NT), 0);
 #pragma unroll
-        for (int z = 0; z < APASS + BPASS; ++z) {
-          __builtin_amdgcn_sched_group_barrier(0x008, (4 * MT * NT) / (APASS + BPASS) > 0 ? (4 * MT * NT) / (APASS + BPASS) : 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        }
+      for (int z = 0; z < APASS + BPASS; ++z) {
+        __builtin_amdgcn_sched_group_barrier(0x008, (4 * MT * NT) / (APASS + BPASS) > 0 ? (4 * MT * NT) / (APASS + BPASS) : 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
     mfma_group(Ab, Bb, 1);
     if constexpr (LOAD) {
       load_tiles();
-      if constexpr (SCHED != 2) {
-        __builtin_amdgcn_sched_group_barrier(0x100, (SCHED == 1 ? 2 : 4) * (MT + NT), 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 4 * (MT + NT), 0);
 #pragma unroll
-        for (int z = 0; z < 4 * MT * NT; ++z) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
-          if (z < APASS + BPASS) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        }
+      for (int z = 0; z < 4 * MT * NT; ++z) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+        if (z < APASS + BPASS) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
     mfma_group(Ab, Bb, 2);
     mfma_group(Ab, Bb, 3);
   };
-  NBM_DBG_T(dbg_t1);
   {
     using T = std::true_type;
     using F = std::false_type;
@@ -719,7 +667,6 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
     if (nk >= 2) { k_step(kt, T{}, F{}); ++kt; }
     k_step(kt, F{}, F{});
   }
-  NBM_DBG_T(dbg_t2);
 
   if (do_bias) {
     const int n = bm0 + (tid % BM);
@@ -743,23 +690,9 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
         atomicAdd(og + (long long)n * p.out_ld + col, v);
       }
   }
-#ifdef NBM_ABLATE_NN
-  __syncthreads();
-  NBM_DBG_ADD(20, dbg_t1 - dbg_t0); NBM_DBG_ADD(21, dbg_t2 - dbg_t1); NBM_DBG_ADD(22, clock64() - dbg_t2); NBM_DBG_ADD(23, 1);
-#endif
 }
 
 }  // namespace
-
-#ifdef NBM_ABLATE_NN
-// timing-only build: read and clear the per-class cycle counters of igemm_nn_kernel (scripts/dgrad_ablate.py)
-extern "C" int nbm_nn_dbg_read(unsigned long long* host24) {
-  unsigned long long z[24] = {0};
-  if (hipMemcpyFromSymbol(host24, HIP_SYMBOL(nbm_nn_dbg), sizeof(z)) != hipSuccess) return -4;
-  if (hipMemcpyToSymbol(HIP_SYMBOL(nbm_nn_dbg), z, sizeof(z)) != hipSuccess) return -4;
-  return NBM_OK;
-}
-#endif
 
 
 static int fill_common(const nbm_bwd_desc* d, BwdParams& p) {
@@ -829,20 +762,15 @@ extern "C" int nbm_conv_dgrad(const nbm_bwd_desc* d, void* stream) {
     }
     p.m_tiles = 4 * tmax;
   }
-#ifdef NBM_ABLATE_NN
-  p.ablate = getenv("NBM_NN_ABLATE") ? atoi(getenv("NBM_NN_ABLATE")) : 0;       // read per call: the probe switches it between launches
-#endif
   hipStream_t st = (hipStream_t)stream;
-  // short K (<= 8 steps of 32) and a 16-byte epilogue: the three-workgroups-per-CU variant (see the template comment)
-  static const int shortk_max = getenv("NBM_NN_SHORTK_MAX") ? atoi(getenv("NBM_NN_SHORTK_MAX")) : 8;   // 0 disables
-  // stride 2 (phased): a tile's K loop visits its parity class's taps only -- (N / 32) x {1, 2, 2, 4} steps for a 3x3
+  // short K (<= 8 steps of 32) and a 16-byte epilogue: the three-workgroups-per-CU variant (see the template comment).
+  // Stride 2 (phased): a tile's K loop visits its parity class's taps only -- (N / 32) x {1, 2, 2, 4} steps for a 3x3; up to 16 steps
   // (the largest class's step count decides: 128 -> 128 @94x256, steps 4 / 8 / 8 / 16: 3.61 -> 3.46 ms at B = 128 on the single-stage kernel)
-  static const int shortk_ph = getenv("NBM_NN_SHORTK_PHASED") ? atoi(getenv("NBM_NN_SHORTK_PHASED")) : 16;
   const int ph_max = ((d->N + BK - 1) / BK) * ((d->kh + 1) / 2) * ((d->kw + 1) / 2);
   // the 64-wide tile spends half the MFMA cycles per K-step: its prologue / epilogue weigh double, and the third workgroup pays up to
-  // K = 576 (layer1's 3x3 64 -> 64 @94x256 at B = 128: 2.39 -> 2.15 ms, round 5)
-  const int shortk_lim = d->Cin <= 64 && shortk_max ? (shortk_max > 20 ? shortk_max : 20) : shortk_max;
-  const bool shortk = p.vec_epi && (p.phased ? ph_max <= shortk_ph : ((d->N + BK - 1) / BK) * d->kh * d->kw <= shortk_lim);
+  // K = 576 (layer1's 3x3 64 -> 64 @94x256 at B = 128: 2.39 -> 2.15 ms, round 5): up to 20 steps there
+  const int shortk_lim = d->Cin <= 64 ? 20 : 8;
+  const bool shortk = p.vec_epi && (p.phased ? ph_max <= 16 : ((d->N + BK - 1) / BK) * d->kh * d->kw <= shortk_lim);
   // deep K: the half-step form of the two-stage kernel (three workgroups per CU, same bits; NBM_NN_H16=0: the two-stage kernel).  Read per
   // call: the parity test flips it inside one process.
   const char* hs_env = getenv("NBM_NN_H16");
@@ -876,18 +804,15 @@ extern "C" int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream) {
   // 128-wide tiles would multiply 64 columns of padding in the last tile (1 / 8 of the MFMA work of 448 columns: 110 against 122 TF/s for
   // the 384-column twin, round 5) -- the first Cin - 64 columns on 128-wide tiles, the last 64 on the 64-wide kernel.  Same sums per element
   // (the split over the pixels is chosen per launch; the atomics make the order free anyway).
-  {
-    static const int tail_split = getenv("NBM_TN_TAIL") ? atoi(getenv("NBM_TN_TAIL")) : 1;
-    if (tail_split && taps == 1 && d->stride == 1 && d->pad == 0 && !p.b_generic && d->Cin > 128 && (d->Cin & 127) == 64) {
-      nbm_bwd_desc a = *d, b = *d;
-      a.Cin = d->Cin - 64;
-      b.Cin = 64;
-      b.x = d->x + (d->Cin - 64);
-      b.out = d->out + (d->Cin - 64);
-      b.bias_grad = nullptr;                                   // (the column sums of G come from the first launch)
-      rc = nbm_conv_wgrad(&a, stream);
-      return rc ? rc : nbm_conv_wgrad(&b, stream);
-    }
+  if (taps == 1 && d->stride == 1 && d->pad == 0 && !p.b_generic && d->Cin > 128 && (d->Cin & 127) == 64) {
+    nbm_bwd_desc a = *d, b = *d;
+    a.Cin = d->Cin - 64;
+    b.Cin = 64;
+    b.x = d->x + (d->Cin - 64);
+    b.out = d->out + (d->Cin - 64);
+    b.bias_grad = nullptr;                                   // (the column sums of G come from the first launch)
+    rc = nbm_conv_wgrad(&a, stream);
+    return rc ? rc : nbm_conv_wgrad(&b, stream);
   }
   p.M = d->B * d->Ho * d->Wo;
   const bool narrow_m = d->N <= 64 && !p.b_generic;            // 64-row dW tiles: no MFMA spent on the zero half of a 128-row G tile
@@ -904,7 +829,7 @@ extern "C" int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream) {
   const int max_splits = (p.M + 8 * BK - 1) / (8 * BK);
   // (512 = 256 CUs x the two workgroups of the 128 x 128 instantiation.  The narrower instantiations hold 3 or 4 per CU; sizing the rounds
   // for 768 / 1024 was measured in round 5 and changes nothing -- 2.161 vs 2.155 ms on layer1's 3x3: a CU with fewer workgroups left runs
-  // them faster, the matrix pipe is what they share -- scripts/wgrad_cycles.py)
+  // them faster, the matrix pipe is what they share -- scripts/wgrad_cycles.py, in the git history)
   const int slots = 512;
   int splits = 1;
   double best = -1.0;
@@ -951,17 +876,12 @@ extern "C" int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream) {
                     (long long)BK * d->x_ld * 4 < 0x40000000ll;
   if (p.b_generic) hipLaunchKernelGGL((igemm_tn_kernel<64, B_GENERIC>), grid, dim3(256), 0, st, p);
   else if (narrow_m) {
-    if (wide && same) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 0, 64>), grid, dim3(256), 0, st, p);
-    else if (wide) hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED, 0, 64>), grid, dim3(256), 0, st, p);
-    else if (same) hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME, 0, 64>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED, 0, 64>), grid, dim3(256), 0, st, p);
+    if (wide && same) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 64>), grid, dim3(256), 0, st, p);
+    else if (wide) hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED, 64>), grid, dim3(256), 0, st, p);
+    else if (same) hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME, 64>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED, 64>), grid, dim3(256), 0, st, p);
   }
-  else if (wide && same) {
-    static const int sched = getenv("NBM_TN_SCHED") ? atoi(getenv("NBM_TN_SCHED")) : 0;
-    if (sched == 1) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 1>), grid, dim3(256), 0, st, p);
-    else if (sched == 2) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 2>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME>), grid, dim3(256), 0, st, p);
-  }
+  else if (wide && same) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME>), grid, dim3(256), 0, st, p);
   else if (wide) hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED>), grid, dim3(256), 0, st, p);
   else if (same) hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME>), grid, dim3(256), 0, st, p);
   else hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED>), grid, dim3(256), 0, st, p);

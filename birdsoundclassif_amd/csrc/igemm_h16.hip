@@ -22,8 +22,7 @@ constexpr int BM = 128, BN = 128, WM = 64, WN = 64, MT = 2, NT = 2;
 constexpr int P16 = 20;      // floats per LDS row (16 + 4 pad: conflict-free ds_read_b128 of 16 consecutive rows)
 enum { EPI_STD = 0 };
 
-template <int OCC>
-__global__ __launch_bounds__(256, OCC) void igemm_h16_kernel(const IgemmParams p) {
+__global__ __launch_bounds__(256, 3) void igemm_h16_kernel(const IgemmParams p) {
   constexpr int STAGES = 1, EPI = EPI_STD;          // (names the shared epilogue text expects: the tile goes out in two halves)
   constexpr bool ROWS = false;
   __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * P16];
@@ -183,12 +182,11 @@ __global__ __launch_bounds__(256, OCC) void igemm_h16_kernel(const IgemmParams p
 
 }  // namespace
 
-int nbm_igemm::h16_launch(const IgemmParams& p0, int groups, int occ, hipStream_t st) {
+int nbm_igemm::h16_launch(const IgemmParams& p0, int groups, hipStream_t st) {
   IgemmParams p = p0;
   p.m_tiles = (p.M + BM - 1) / BM;
   p.n_tiles = (p.N + BN - 1) / BN;
   const dim3 grid(p.m_tiles * p.n_tiles, 1, groups);
-  if (occ >= 4) hipLaunchKernelGGL((igemm_h16_kernel<4>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((igemm_h16_kernel<3>), grid, dim3(256), 0, st, p);
+  hipLaunchKernelGGL(igemm_h16_kernel, grid, dim3(256), 0, st, p);
   return nbm_launch_status();
 }

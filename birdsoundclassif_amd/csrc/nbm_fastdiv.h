@@ -6,7 +6,7 @@
 // multiplier and two shifts (Granlund-Montgomery, round-up method: exact for every 32-bit n and every d >= 1), the kernel spends five
 // integer instructions instead of the ~35 of a run-time v_rcp-based division.  The tile prologues decode 4-5 GEMM rows into (image, y, x)
 // each and the data-gradient kernel divided by the stride once per (row, tap): 25-55 k cycles per tile before the first MFMA (round 5,
-// cycle counters in the `ablate_nn` build), as long as the whole K loop of the short-K layers.
+// cycle counters of a timing-only attribution build), as long as the whole K loop of the short-K layers.
 struct nbm_fastdiv { unsigned mul, sh1, sh2; };
 static inline nbm_fastdiv nbm_fastdiv_make(unsigned d) {
   nbm_fastdiv f{1u, 0u, 0u};

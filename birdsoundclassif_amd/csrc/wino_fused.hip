@@ -22,12 +22,6 @@
 #include "nbm_common.h"
 #include <type_traits>
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define NBM_KEEP(x) asm volatile("" : "+v"(x))      // the value stays live and opaque (timing-only ablations)
-#else
-#define NBM_KEEP(x) (void)(x)
-#endif
-
 namespace {
 
 constexpr int BK = 32;
@@ -132,11 +126,9 @@ __global__ __launch_bounds__(256) void wino23_rows_tiles_kernel(const float* __r
   }
 }
 
-// ABL: timing-only ablations for scripts/wino_fused_probe.py (results are wrong): 1 = no flush, 2 = no epilogue,
-// 4 = every workgroup reads the same L2-resident A tile
 // BM: tile rows of the block (128; 96 for dense launches whose 128-row blocks would leave the last round of resident workgroups
 // half empty -- one wave row of 96 x 32 patches, MT = 3, NT = 1; an output sums its planes and K-steps in the same order in every shape)
-template <int BM, int BN, int WM, int WN, int ABL = 0>
+template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(const WinoFusedParams p) {
   constexpr int MT = WM / 32, NT = WN / 32;
   constexpr int WAVES_N = BN / WN;
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
     const int n = bn0 + r0 + 32 * i;
     b_rel[i] = n < p.N ? (unsigned)((n * p.C + c4 * 4) * 4) : 0x80000000u;
   }
-  const float* a_plane0 = (ABL & 4) ? p.R : p.R + blk_base;
+  const float* a_plane0 = p.R + blk_base;
   const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.U), 0, 0x7ffffff0, 0x00020000);
 
   f32x4 ra[AR], ra2[AR], rb[BR];
@@ -217,7 +209,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
     const int i = ld_xi >> 2, j = ld_xi & 3;
     const int k1 = j == 0 ? 0 : (j == 2 ? 2 : 1), k2 = j == 2 ? 1 : (j == 3 ? 3 : 2);
     const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a_plane0 + ((ABL & 4) ? 0ll : (long long)i * p.r_gs)), 0, 0x7ffffff0, 0x00020000);
+        const_cast<float*>(a_plane0 + (long long)i * p.r_gs), 0, 0x7ffffff0, 0x00020000);
     const unsigned a_soff1 = (unsigned)((k1 * p.C + ld_c0) * 4), a_soff2 = (unsigned)((k2 * p.C + ld_c0) * 4);
     const unsigned b_soff = (unsigned)((ld_xi * p.u_gs + ld_c0) * 4);
 #pragma unroll
@@ -265,7 +257,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
 
   // One K-step = 4 groups of 4 k-pairs.  The fragments of group q + 1 are read from LDS while the 4 MT NT MFMAs of group q
   // run (register double buffer fa / fb).  sched_group_barrier pins the interleave below: without it the same code runs
-  // 19 % slower.  Measured and dropped (scripts/wino_fused_probe.py, 188x512 x 26 images, 16.2 ms as is): three LDS stages
+  // 19 % slower.  Measured and dropped (scripts/wino_fused_probe.py, in the git history; 188x512 x 26 images, 16.2 ms as is): three LDS stages
   // with the barrier behind the LDS writes, so that the first fragments of step k+1 are prefetched in G3 of step k
   // (18.9 ms: the compiler bunches G0's MFMAs and spills); plane-dependent scalars (buffer descriptor, column offsets)
   // kept as loop-carried state instead of being re-derived every step (17.9 ms: the conditional update splits the step's
@@ -377,26 +369,9 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
       k_step(TT{}, FF{});
       k_step(FF{}, FF{});
     }
-    if constexpr (!(ABL & 1)) {
-      flush(xi);
-    } else {                                   // keep the plane product alive (cdna guide rule 17) without the VALU work
-#pragma unroll
-      for (int a = 0; a < MT; ++a)
-#pragma unroll
-        for (int b = 0; b < NT; ++b) NBM_KEEP(acc[a][b]);
-    }
+    flush(xi);
   }
   __syncthreads();
-  if constexpr (ABL & 2) {
-#pragma unroll
-    for (int a = 0; a < MT; ++a)
-#pragma unroll
-      for (int b = 0; b < NT; ++b) {
-        NBM_KEEP(acc[a][b]);
-        NBM_KEEP(Y[0][0][a][b]); NBM_KEEP(Y[0][1][a][b]); NBM_KEEP(Y[1][0][a][b]); NBM_KEEP(Y[1][1][a][b]);
-      }
-    return;
-  }
 
   // ---- epilogue: four passes (p, q) through an LDS-staged [128 tiles][BN] tile, 16-byte stores along the channels.
   // C/D layout of the 32x32 MFMA: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
@@ -550,14 +525,7 @@ static int wino23_conv_fused_launch(const float* R, const float* U, const float*
   p.tiles = tiles; p.n_blocks = n_blocks; p.blk_info = blk_info;
   if (tiles) { p.T = n_entries; p.m_tiles = n_entries / LIST_BM; }
   hipStream_t st = (hipStream_t)stream;
-  // `variant`: 0 = automatic, 128 / 64 = channel-tile width; anything else is refused.  The timing-only ablations of
-  // scripts/wino_fused_probe.py (variant + 1000 * ABL: WRONG results by design) exist only in a -DNBM_ABLATE build
-  // (make ablate -> libnbm_hip_ablate.so), never in the shipped library.
-  int abl = 0;
-#ifdef NBM_ABLATE
-  abl = variant / 1000;
-  variant %= 1000;
-#endif
+  // `variant`: 0 = automatic, 128 / 64 = channel-tile width; anything else is refused.
   if (variant != 0 && variant != 64 && variant != 128) return NBM_EINVAL;
   const bool wide = variant == 128 || (variant == 0 && N % 128 == 0);
   p.n_tiles = wide ? (N + 127) / 128 : (N + 63) / 64;
@@ -578,21 +546,10 @@ static int wino23_conv_fused_launch(const float* R, const float* U, const float*
     p.m_tiles = (int)((T + bm - 1) / bm);
   }
   const dim3 grid((n_blocks ? (p.m_tiles + 7) / 8 * 8 : p.m_tiles) * p.n_tiles), block(256);
-#define NBM_WF(BM_, BN_, WM_, WN_, A_) hipLaunchKernelGGL((wino23_fused_kernel<BM_, BN_, WM_, WN_, A_>), grid, block, 0, st, p)
-#ifdef NBM_ABLATE
-  if (wide) {
-    switch (abl) { case 0: NBM_WF(128, 128, 64, 64, 0); break; case 1: NBM_WF(128, 128, 64, 64, 1); break; case 2: NBM_WF(128, 128, 64, 64, 2); break;
-                   case 3: NBM_WF(128, 128, 64, 64, 3); break; case 7: NBM_WF(128, 128, 64, 64, 7); break; default: return NBM_EINVAL; }
-  } else {
-    switch (abl) { case 0: NBM_WF(128, 64, 64, 32, 0); break; case 1: NBM_WF(128, 64, 64, 32, 1); break; case 2: NBM_WF(128, 64, 64, 32, 2); break;
-                   case 3: NBM_WF(128, 64, 64, 32, 3); break; case 7: NBM_WF(128, 64, 64, 32, 7); break; default: return NBM_EINVAL; }
-  }
-#else
-  (void)abl;
-  if (!wide) NBM_WF(128, 64, 64, 32, 0);
-  else if (bm == 96) NBM_WF(96, 128, 96, 32, 0);
-  else NBM_WF(128, 128, 64, 64, 0);
-#endif
+#define NBM_WF(BM_, BN_, WM_, WN_) hipLaunchKernelGGL((wino23_fused_kernel<BM_, BN_, WM_, WN_>), grid, block, 0, st, p)
+  if (!wide) NBM_WF(128, 64, 64, 32);
+  else if (bm == 96) NBM_WF(96, 128, 96, 32);
+  else NBM_WF(128, 128, 64, 64);
 #undef NBM_WF
   return nbm_launch_status();
 }

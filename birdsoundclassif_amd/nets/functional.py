@@ -34,12 +34,11 @@ def _pad32_rows(g2d, n):
 # instead of a zero fill of a temporary, the kernel, and autograd's AccumulateGrad add into the same view (~100 fills + ~100 adds of a
 # B = 128 step).  The optimiser's post-accumulate hook is called by hand (`mark`), since autograd never sees the gradient.
 GRAD_SINK = {}          # data_ptr of a parameter -> (weakref to it, mark)
-DIRECT_WGRAD = os.environ.get('NBM_DIRECT_WGRAD', '1') != '0'
 
 
 def grad_sink(param, rows, cols):
     """-> ([rows][cols] view of the parameter's own zero-initialised gradient, mark) or None."""
-    if not DIRECT_WGRAD or param is None or not torch.is_tensor(param):
+    if param is None or not torch.is_tensor(param):
         return None
     e = GRAD_SINK.get(param.data_ptr())
     if e is None:
@@ -91,8 +90,7 @@ def _w_to_ref_layout(gw, weight):
     return gw[:, :kh * kw * c].view(n, kh, kw, c).permute(0, 3, 1, 2)
 
 
-STEM_FOLDED = True       # init_conv folded into conv1 (csrc/stem.hip); False: init_conv kernel + generic implicit GEMM
-WINO_MIN_CIN = int(__import__('os').environ.get('NBM_WINO_MIN_CIN', '128'))   # 64-channel 3x3 layers: measured, see DESIGN 5
+WINO_MIN_CIN = 128       # 64-channel 3x3 layers stay on the implicit GEMM: measured, see DESIGN 5
 WINOGRAD = True          # module switch for A/B tests (tests/test_gpu_e2e.py compares both convolution paths)
 GRAD_SHARE = True        # the two consumers of an FPN map accumulate their gradients into one buffer (RoiPool / DwConv)
 _GRAD_ACC = {}           # data_ptr of an FPN map -> weak reference to the gradient map the RoI pooling's backward pass filled
@@ -106,7 +104,6 @@ WINO_BWD_TILE = 4        # F(4x4,3x3) for the two backward convolutions (gradien
 # consumer whose backward node runs FIRST (the one created later: autograd runs ready nodes by descending sequence number, and the
 # FPN nodes never wait for a backbone node) leaves its gradient here and returns None; the other consumer, which registered itself in
 # the forward pass (`stash_accept`), adds it in the epilogue of the kernel that produces its own gradient (`residual`).
-GRAD_STASH = True
 _STASH = {}              # data_ptr -> gradient left by the first consumer's backward pass
 _STASH_OK = {}           # data_ptr -> shape of the tensors whose OTHER consumer will pick a stashed gradient up (this forward pass)
 
@@ -117,8 +114,6 @@ _STASH_OK = {}           # data_ptr -> shape of the tensors whose OTHER consumer
 # hands it is that very tensor, untouched -- a sum with a third consumer's share is another tensor or (accumulated in place) another
 # version, and is then masked again, which changes nothing.
 _PREMASKED = {}
-PREMASK = True           # module switch for A/B measurements (scripts/trainloop.py)
-HALF_RES_SHORTCUT = True  # Bottleneck.backward: a stride-2 shortcut's data gradient stays at half resolution (A/B switch)
 UPBWD_SPLIT_READ = True   # the finest lateral's node reads a split gradient (ondemand.UPBWD_SPLIT) as it is; False: it puts the RoI share
                           # into the map first and reads that densely (A/B switch, and the fallback's test)
 
@@ -228,14 +223,14 @@ def pass_check_owner(model, what):
 def stash_accept(t, needs_grad):
     """Called from the forward pass of the consumer that will pick the stash up; `needs_grad` = ctx.needs_input_grad of `t`
     (inside Function.forward grad mode is off, so torch.is_grad_enabled() says nothing)."""
-    if GRAD_STASH and needs_grad:
+    if needs_grad:
         _STASH_OK[t.data_ptr()] = tuple(t.shape)
         return True
     return False
 
 
 def _stash_wanted(t):
-    return bool(GRAD_STASH and t is not None and _STASH_OK.get(t.data_ptr()) == tuple(t.shape))
+    return bool(t is not None and _STASH_OK.get(t.data_ptr()) == tuple(t.shape))
 
 
 def stash_check_empty():
@@ -292,14 +287,14 @@ class Conv(Function):
             # the RoIs when the RoI pooling asks for them; the backward pass is the dense one (the incoming gradient is
             # zero wherever nothing was read)
             y, ctx.lazy = ondemand.conv3x3_winograd_lazy(x, _prep.wino23(weight), sh, lazy_stride[0],
-                                                         _prep.cell_weight(weight, forward=True) if ondemand.CELL_FWD else None,
+                                                         _prep.cell_weight(weight, forward=True),
                                                          fold=lambda wk, alpha, transposed=False: _prep.cell_weight_folded(weight, wk, alpha, transposed),
                                                          keep=lazy_stride[1], raw=(weight, bias))
         elif lazy_stride and kh == 1:
             # the lateral 1x1 (+ top-down merge) in front of a demand-driven 3x3: only the pixels that convolution reads
             # deferred: write nothing, the consumer takes t / up / the weights into its cell-domain GEMMs -- provided its backward
             # pass (if one can follow) is the cell-domain one, the only one that does not read the pattern patches of this map
-            defer = not any(ctx.needs_input_grad) or (ondemand.CELL_BWD and LAZY_WGRAD and LAZY_DGRAD)
+            defer = not any(ctx.needs_input_grad) or (LAZY_WGRAD and LAZY_DGRAD)
             y = ondemand.conv1x1_lazy(x, _prep.krsc(weight), sh, alpha, up, lazy_stride[0], defer=defer)
             hit = ondemand._LAZY_LATERAL.get(y.data_ptr())
             ctx.lat_state = hit[0] if hit is not None else None      # its consumer's backward pass may leave this node's gradients there
@@ -363,7 +358,7 @@ class Conv(Function):
             # within a pixel of them -> the listed fused kernel on the tiles around them (F(2x2,3x3), no transforms through HBM)
             other = _STASH.pop(x.data_ptr(), None) if ctx.take_x else None       # overlap level: taken over as the accumulation base
             gx = ondemand.conv3x3_winograd_dgrad_tiles(ctx.lazy, g.view(B, H, W, N), _prep.wino23(weight, transposed=True, m=2),
-                                                       _prep.cell_weight(weight) if ondemand.CELL_BWD else None, base=other,
+                                                       _prep.cell_weight(weight), base=other,
                                                        lateral_grads=LAZY_WGRAD and ctx.needs_input_grad[1])
         elif ctx.needs_input_grad[0] and ctx.wino and N % 32 == 0:
             # data gradient of a 3x3 / stride 1 / pad 1 convolution = the same convolution with the kernel rotated by 180
@@ -530,8 +525,8 @@ class Bottleneck(Function):
             if need[4]:
                 gwd = wgrad(g3r, x, kd, wd, sd, B=B, H=H, W=W, Cin=Cin, N=N3, stride=stride)
             other = _STASH.pop(x.data_ptr(), None) if ctx.take_x else None     # the FPN lateral's share of d/dx (see _STASH)
-            premask = PREMASK and other is not None                      # d/dx is complete below: mask it here (see _PREMASKED)
-            if stride == 2 and HALF_RES_SHORTCUT and Cin % 4 == 0:
+            premask = other is not None                                  # d/dx is complete below: mask it here (see _PREMASKED)
+            if stride == 2 and Cin % 4 == 0:
                 # strided 1x1: only the (even, even) pixels have a tap -> its data gradient stays at ITS resolution (a plain GEMM
                 # over the Ho x Wo grid) and the block's last data-gradient kernel adds it there (`residual2`), next to the
                 # lateral's share: no full-resolution map that is 3/4 a copy (4.5 -> 1.7 ms for layer2.0 at B = 128)
@@ -561,7 +556,7 @@ def conv(x, weight, bias=None, scale=None, shift=None, residual=None, kh=1, kw=1
     pixels they read are computed (3x3 Winograd layers only; ignored elsewhere)."""
     if lazy_stride and kh == 1:       # lateral in front of the demand-driven convolution (ondemand.conv1x1_lazy)
         Cin, N = x.shape[-1], weight.shape[0]
-        if not (ondemand.LAZY_FINEST and ondemand.LAZY_LATERAL and kw == 1 and stride == 1 and pad == 0 and weight.dim() == 4 and scale is None
+        if not (ondemand.LAZY_FINEST and kw == 1 and stride == 1 and pad == 0 and weight.dim() == 4 and scale is None
                 and residual is None and act == ACT_NONE and Cin % 32 == 0 and Cin <= 256 and N > 64 and N % 4 == 0):
             lazy_stride = None
     elif lazy_stride and not (ondemand.LAZY_FINEST and _winograd_ok(x, weight, kh, kw, stride, pad) and x.shape[-1] >= 64):
@@ -678,15 +673,11 @@ class Stem(Function):
     """init_conv (1 -> 3, 1x1 + bias) followed by conv1 7x7/s2 + FrozenBN + ReLU (reference backbone.py:104-113 and
     torchvision's stem).  Backward never forms the 3-channel data gradient: with U[n,t] = sum_m g[m,n] x[pix(m)+t] and
     V[n,t] = sum_m g[m,n] [pix(m)+t inside], dW1[n,c,t] = w_c U + b_c V, dw_c = sum W1[n,c,t] U, db_c = sum W1[n,c,t] V;
-    U and V are ONE weight-gradient launch over the 2-channel image (x, 1)."""
+    U and V come from ONE kernel over the 1-channel image (ops.stem7x7_wgrad)."""
 
     @staticmethod
     def forward(ctx, x, w_init, b_init, w1, scale, shift):
-        if STEM_FOLDED and w1.shape[0] == 64 and x.shape[-1] == 1:
-            y = ops.stem7x7(x, *_prep.stem_fold(w1, w_init, b_init), scale, shift)      # one kernel on the 1-channel image
-        else:
-            y0 = ops.init_conv(x, w_init.detach(), b_init.detach())
-            y = ops.conv2d(y0, _prep.krsc(w1), 7, 7, 2, 3, scale=scale, shift=shift, act=ACT_RELU)
+        y = ops.stem7x7(x, *_prep.stem_fold(w1, w_init, b_init), scale, shift)      # one kernel on the 1-channel image
         ctx.save_for_backward(x, w_init, b_init, w1, scale, y)
         return y
 
@@ -695,17 +686,8 @@ class Stem(Function):
     def backward(ctx, gy):
         x, w_init, b_init, w1, scale, y = ctx.saved_tensors
         g = gy.contiguous() if _premasked(y, gy) else ops.relu_bwd(gy.contiguous(), y)
-        B, H, W, _ = x.shape
-        if STEM_FOLDED and w1.shape[0] == 64 and x.shape[-1] == 1:
-            U, V = ops.stem7x7_wgrad(x, g)                                # one MFMA kernel over the 1-channel image (stem.hip)
-            U, V = U * scale.view(64, 1, 1), V * scale.view(64, 1, 1)
-        else:
-            x2 = torch.ones((B, H, W, 2), device=x.device, dtype=torch.float32)
-            x2[..., 0] = x[..., 0]
-            uv = torch.zeros((64, 7 * 7 * 2), device=x.device, dtype=torch.float32)
-            ops.conv_wgrad(g.view(-1, 64), x2, uv, B=B, H=H, W=W, Cin=2, N=64, kh=7, kw=7, stride=2, pad=3, row_scale=scale)
-            uv = uv.view(64, 7, 7, 2)
-            U, V = uv[..., 0], uv[..., 1]                                 # [64,7,7]
+        U, V = ops.stem7x7_wgrad(x, g)                                    # one MFMA kernel over the 1-channel image (stem.hip)
+        U, V = U * scale.view(64, 1, 1), V * scale.view(64, 1, 1)
         wi, bi = w_init.detach().view(3), b_init.detach().view(3)
         gw1 = wi.view(1, 3, 1, 1) * U[:, None] + bi.view(1, 3, 1, 1) * V[:, None]
         w1d = w1.detach()
@@ -731,7 +713,7 @@ class MaxPool(Function):
     def backward(ctx, gy):
         idx, x = ctx.saved_tensors
         other = _STASH.pop(ctx.x_ptr, None) if ctx.take_x else None     # the lateral's share of d/dx, added in the kernel
-        premask = PREMASK and ctx.premask and other is not None
+        premask = ctx.premask and other is not None
         gx = ops.maxpool3x3s2_bwd(idx, gy.contiguous(), *ctx.hw, residual=other, mask=x if premask else None)
         ondemand.zero_recycle(other)                  # the lateral's share may be a persistent map (ondemand.zero_acquire)
         if premask:
@@ -815,7 +797,7 @@ class DwConv(Function):
             # pass (a persistent map for the demand-driven level, see ondemand.zero_acquire; the taps' 3x3 blocks are its footprint)
             st = ondemand.lazy_state(x)
             acc = e = None
-            if (ondemand.ZERO_POOL and LAZY_DGRAD and LAZY_WGRAD and ondemand.CELL_BWD and st is not None and st.sparse and st.keep and
+            if (ondemand.ZERO_POOL and LAZY_DGRAD and LAZY_WGRAD and st is not None and st.sparse and st.keep and
                     st.stride >= 5 and stride >= 3):
                 acc, e = ondemand.zero_acquire(tuple(x.shape), x.device, ('map-grad', st.stride))
                 if acc is not None:
@@ -868,7 +850,7 @@ class RpnComposite(Function):
             ptr = ctx.fm_ptr
             if EARLY and ptr in _FPN_OUT and GRAD_SHARE:
                 acc = e = None
-                if (ondemand.ZERO_POOL and LAZY_DGRAD and LAZY_WGRAD and ondemand.CELL_BWD and st.keep and
+                if (ondemand.ZERO_POOL and LAZY_DGRAD and LAZY_WGRAD and st.keep and
                         ((st.sparse and st.stride >= 5) or st.overlap)):
                     acc, e = ondemand.zero_acquire(ctx.fm_shape, gf.device, ('map-grad', st.stride))      # persistent zeros: no fill
                 if acc is None:
@@ -968,7 +950,7 @@ class RoiPool(Function):
         # demand-driven levels whose backward pass goes through the cell transforms: their gradient maps are persistent
         # (ondemand.zero_acquire); the map's producer (Conv.backward) recycles them
         ctx.pooled = {}
-        if ondemand.ZERO_POOL and GRAD_SHARE and LAZY_DGRAD and LAZY_WGRAD and ondemand.CELL_BWD:
+        if ondemand.ZERO_POOL and GRAD_SHARE and LAZY_DGRAD and LAZY_WGRAD:
             for i, f in enumerate(fmaps):
                 st = ondemand.lazy_state(f)
                 # (an overlap level read by the composed RPN block, Fn.RpnComposite: nothing but the RoI windows is ever written to its

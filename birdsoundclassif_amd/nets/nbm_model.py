@@ -16,7 +16,6 @@ from .self_attention import build_sa_layers, materialize
 from .head import build_head
 from .. import ops
 
-DEFER_PROJECTION_TRAIN = os.environ.get('NBM_DEFER_PROJECTION_TRAIN', '1') != '0'
 DEFER_PROJECTION = os.environ.get('NBM_DEFER_PROJECTION', '1') != '0'      # evaluation mode: attention's final projection folded into the FPN laterals
 
 
@@ -37,8 +36,7 @@ class NbmModel(nn.Module):
         Level 0 (stride 8): three 2x2 tiles out of four are never read.  Level 1 (stride 4): every tile holds a pattern pixel, so
         the listed F(2x2,3x3) tiles gained nothing there (round 2: 10.1 -> 8.5 ms at B = 64, eaten by the RoI phase); with the
         pattern pixels going through the cell transforms (csrc/cellwino.hip: 25 plane products per 4x4 cell instead of the 64 of
-        its four tiles) it pays: detect step 81.4 -> 75.6 ms at B = 64.  NBM_LAZY_LEVEL1=0 keeps level 1 dense."""
-        from .. import ondemand
+        its four tiles) it pays: detect step 81.4 -> 75.6 ms at B = 64."""
         a = self.args
         if getattr(a, 'fpn_first', False) or getattr(a, 'sandwich_attn', False) or getattr(a, 'fpn', 'fpn') != 'fpn':
             return None
@@ -46,7 +44,7 @@ class NbmModel(nn.Module):
         if not (st >= 6 and st == int(st)):
             return None
         out = {0: int(st)}
-        if ondemand.CELL_FWD and os.environ.get('NBM_LAZY_LEVEL1', '1') != '0' and int(st) % 2 == 0 and int(st) // 2 >= 3:
+        if int(st) % 2 == 0 and int(st) // 2 >= 3:
             out[1] = int(st) // 2
         return out
 
@@ -70,8 +68,8 @@ class NbmModel(nn.Module):
         if getattr(self.args, 'sandwich_attn', False):
             return materialize(self.attn[1](self.fpn(self.attn[0](features))))
         # evaluation mode, plain FPN: the attention levels' final projection is folded into the FPN's laterals (self_attention.Projected)
-        # (with a gradient to come: module + lateral as one composed tape node, functional.AttnLateral -- NBM_DEFER_PROJECTION_TRAIN=0: off)
-        defer = type(self.fpn).__name__ == 'FPN' and DEFER_PROJECTION and (not torch.is_grad_enabled() or DEFER_PROJECTION_TRAIN)
+        # (with a gradient to come: module + lateral as one composed tape node, functional.AttnLateral)
+        defer = type(self.fpn).__name__ == 'FPN' and DEFER_PROJECTION
         levels = self.attn(features, defer_projection=self.fpn.pt_wise) if defer else self.attn(features)
         if lazy and self._lazy_strides():
             out = self.fpn(levels, lazy_strides=self._lazy_strides())

@@ -19,7 +19,6 @@ from . import ops
 from .ops import check, lib, _ptr, _chk, _stream, gemm_conv, conv_wgrad
 
 LAZY_FINEST = os.environ.get('NBM_LAZY_FINEST', '1') != '0'
-LAZY_LATERAL = os.environ.get('NBM_LAZY_LATERAL', '1') != '0'      # also the lateral 1x1 + merge in front of the map
 LAZY_POISON = False                 # tests: fill the map with NaN first, so that a read of an unwritten pixel shows
 _LAZY = {}                          # data_ptr of the sparse map -> LazyMap
 _PATTERNS = {}
@@ -264,9 +263,6 @@ def _forget(table, key, ident):
         del table[key]
 
 
-FUSED_FINEST = os.environ.get('NBM_FUSED_FINEST', '1') != '0'     # the lateral's operands go into the consumer's cell-domain GEMMs
-
-
 def _lateral_pattern_pass(x, ls, stride):
     """The lateral + merge on the pattern patches (`TilePattern.px_rows`) into the sparse map x."""
     B, H, W, N = x.shape
@@ -292,7 +288,7 @@ def conv1x1_lazy(t, wk, bias, alpha, up, stride, defer=False):
     B, H, W, Cin = t.shape
     N = wk.shape[0]
     x = _sparse_map((B, H, W, N), t.device)
-    defer = bool(defer and FUSED_FINEST and CELL_FWD and up is not None and stride >= 3 and Cin % 4 == 0 and N % 32 == 0 and
+    defer = bool(defer and up is not None and stride >= 3 and Cin % 4 == 0 and N % 32 == 0 and
                  (N + Cin) % 32 == 0 and wk.shape[1] == Cin)
     ls = LateralState(t, wk, bias, alpha, up, deferred=defer, stride=stride)
     if not defer:
@@ -302,9 +298,6 @@ def conv1x1_lazy(t, wk, bias, alpha, up, stride, defer=False):
     _LAZY_LATERAL[x.data_ptr()] = (ls, weakref.ref(x))
     weakref.finalize(x, _forget, _LAZY_LATERAL, x.data_ptr(), id(ls))
     return x
-
-
-CELL_FWD = os.environ.get('NBM_CELL_FWD', '1') != '0'     # pattern pixels of the FORWARD pass through the cell transforms
 
 
 def _cell_operand(st, b0, nb, H, W, C_, x, n_out=0, ci=None):
@@ -334,7 +327,7 @@ def _cell_operand(st, b0, nb, H, W, C_, x, n_out=0, ci=None):
         return V, M, K, T
     if st.vx is not None and ci in st.vx:                # the forward pass left it here
         return st.vx.pop(ci), ops._wino_scratch(x.device, 25 * T * n_out, 0)[0], C_, T
-    if st.keep and ci is not None and n_out and (st.sparse or st.overlap) and CELL_BWD:
+    if st.keep and ci is not None and n_out and (st.sparse or st.overlap):
         # forward pass, the cell-domain weight gradient will want the same operand (7.5 GB at B = 128 for level P2: -2.4 ms)
         if st.vx is None:
             st.vx = {}
@@ -382,7 +375,7 @@ def conv3x3_winograd_lazy(x, U, bias, stride, Ucell=None, fold=None, keep=False,
     defer_pattern = bool(COMPOSITE and cell_ok and raw is not None and not st.keep and not torch.is_grad_enabled())
     # training: the same reader composed with this convolution in the CELL domain (train_composite_forward): the pattern pass waits too
     # (`keep` was decided with grad mode as the caller sees it; inside Function.forward it is off)
-    defer_train = bool(TRAIN_COMPOSITE and CELL_BWD and cell_ok and raw is not None and st.keep and N % 32 == 0)
+    defer_train = bool(TRAIN_COMPOSITE and cell_ok and raw is not None and st.keep and N % 32 == 0)
     if defer_pattern or defer_train:
         defer_pattern = True
         st.pending = (Ucell, Ufold)
@@ -394,7 +387,7 @@ def conv3x3_winograd_lazy(x, U, bias, stride, Ucell=None, fold=None, keep=False,
         st.sparse = pat.frac < 0.6               # the weight gradient over the listed tiles pays off when most are not listed
         # stride 3 / 4: no tile is free of pattern pixels, but the gradient still lives on 9 / S^2 of the pixels (+ the RoI windows):
         # the cell transforms take that share (overlapping 5x5 patches, added class by class), the listed kernel the RoI share
-        st.overlap = bool(not st.sparse and cell_ok and CELL_BWD and 3 <= stride < 5 and N % 32 == 0)
+        st.overlap = bool(not st.sparse and cell_ok and 3 <= stride < 5 and N % 32 == 0)
         if cell_ok and defer_pattern:
             st.skip = None
             continue
@@ -484,9 +477,6 @@ def _border_classes(nb, H, W, S, device):
     return hit
 
 
-DIRECT_GATHER = os.environ.get('NBM_RPN_DIRECT', '1') != '0'    # rpn_composite: operands that exist as dense maps are gathered by the GEMM itself
-
-
 def rpn_composite(fm, block):
     """Evaluation mode: the output of `block` (layers.DepthwiseSepConv2d, the RPN's reader of the map: depthwise 3x3 / stride S ->
     1x1 -> BatchNorm -> SiLU) on the demand-driven map `fm` WITHOUT the map's pattern pixels: the block composed with the map's own
@@ -523,10 +513,10 @@ def rpn_composite(fm, block):
     # operands: ('patch', c0, c1) = channels [c0, c1) of K from the patch tensor V; ('map', tensor, c0, c1, k0) = channels [c0, c1) of a
     # dense map that are channels [k0, ...) of K
     if lt is not None:
-        direct_t = DIRECT_GATHER and Cin % 32 == 0
+        direct_t = Cin % 32 == 0
         operands = [('patch', 0, C_)] + ([('map', lt.t, 0, Cin, C_)] if direct_t else [])
         KV = C_ if direct_t else K                  # channels held by the patch tensor
-    elif DIRECT_GATHER and C_ % 32 == 0:
+    elif C_ % 32 == 0:
         q32 = C_ // 32                               # channel slices (multiples of 32): 3 or 4 links where the channel count allows
         cc = C_ // (3 if q32 % 3 == 0 else 4 if q32 % 4 == 0 else 2 if q32 % 2 == 0 else 1)
         operands = [('map', st.x, c0, c0 + cc, c0) for c0 in range(0, C_, cc)]
@@ -976,7 +966,6 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
     st.done += 1
 
 
-CELL_BWD = os.environ.get('NBM_CELL_BWD', '1') != '0'     # pattern share of both gradients through the cell transforms (cellwino.hip)
 # The deferred lateral's OWN gradients from the consumer's backward pass: its pattern share rides in the cell-domain GEMMs (the
 # folded weights [U | alpha U W] give d/dt in the transform domain, the weight-gradient GEMMs already hold d/d(alpha U W)), its RoI
 # share runs on compact [tiles x 4 pixels] operands -- instead of three dense passes over the 18.9 GB gradient of the merged map
@@ -1080,7 +1069,7 @@ def _cell_outgrad(st, g, ci, b0, nb):
 
 
 def cell_usable(st, H, W, C_, N):
-    return CELL_BWD and (st.stride >= 5 or st.overlap) and C_ % 32 == 0 and N % 32 == 0 and H >= 3 and W >= 3
+    return (st.stride >= 5 or st.overlap) and C_ % 32 == 0 and N % 32 == 0 and H >= 3 and W >= 3
 
 
 def listed_backward(st):
@@ -1097,7 +1086,7 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
     gradient block with the kernel, Toom-Cook in 25 multiplications (cellwino.hip: block transform, 25 grouped GEMMs, patch
     transform into a zero-filled map).  RoI share: the same convolution operator (Ut = weights rotated / channel-swapped,
     F(2x2,3x3)) through the listed fused kernel on the tiles within a pixel of the RoI windows, which reads ALL of g there and
-    so overwrites those tiles with their complete values.  Without `Ucell` (or NBM_CELL_BWD=0) the pattern share also goes
+    so overwrites those tiles with their complete values.  Without `Ucell` the pattern share also goes
     through the listed fused kernel: the static list of the tiles around the pattern (56 % of the tiles, 16 / 12 / 9 planes).
     `st.overlap` (stride 3 / 4: the 5x5 patches of neighbouring cells overlap): the patches are ADDED, one parity class of cells per
     launch, into `base` (the gradient another consumer of the input left, taken over in place) or zeros, and the RoI share -- g

@@ -222,9 +222,6 @@ def release_lane_scratch(keep=(0,)):
         del ondemand._ROI_TILE_BUF[key]
 
 
-WINO_FUSED_VARIANT = int(os.environ.get('NBM_WINO_FUSED_VARIANT', '0'))     # 0 auto, 128 / 64: channel-tile width
-
-
 def conv3x3_winograd(x, U, bias=None, m=2, scale=None, relu=False, mask=None, residual=None):
     """3x3 / stride 1 / pad 1 convolution through Winograd F(m x m, 3x3): x [B,H,W,C], U [(m+2)^2,N,C] from
     `_prep.wino23` -> [B,H,W,N].  m = 2 (the forward setting, error ~3e-6): row half of the input transform (2x the input
@@ -268,7 +265,7 @@ def conv3x3_winograd(x, U, bias=None, m=2, scale=None, relu=False, mask=None, re
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
             check(lib().nbm_wino23_conv_fused(_ptr(V), _ptr(U), _ptr(scale), _ptr(bias), mk, int(relu), nb, H, W, C_, N,
-                                              _ptr(y[b0:b0 + nb]), WINO_FUSED_VARIANT, st), 'nbm_wino23_conv_fused')
+                                              _ptr(y[b0:b0 + nb]), 0, st), 'nbm_wino23_conv_fused')     # variant 0: automatic tile width
             if _prof_fused():
                 e1.record()
                 PROFILE.append(((C_, N, 1, T, 1, 1, nxi, 1, ('wino23', H, W)), e0, e1))

@@ -1,5 +1,5 @@
 """Forward 3x3 64 -> 64 @94x256 (ResNet layer1) and the other 64-wide implicit-GEMM launches: two LDS stages / two workgroups per CU
-against one stage / three (NBM_S1_N64 = largest K / 32 that takes the single-stage kernel).  usage: python scripts/conv64_probe.py [B]"""
+against one stage / three (igemm.hip: up to K = 32 * 20 the single-stage kernel).  usage: python scripts/conv64_probe.py [B]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from birdsoundclassif_amd import ops

@@ -1,5 +1,5 @@
 """Data gradients of the stride-2 convolutions of a B = 128 training step (the 3x3 of the first block of layers 2-4), igemm_nn_kernel
-grouped by parity class.  usage: [NBM_NN_SHORTK_PHASED=n] python scripts/dgrad_s2.py"""
+grouped by parity class.  usage: python scripts/dgrad_s2.py"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from birdsoundclassif_amd import ops

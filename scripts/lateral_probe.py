@@ -18,7 +18,7 @@ for N in (384, 256, 128, 512):
         ts.append(s.elapsed_time(e))
     t = min(ts[1:])
     gb = 4.0 * B * H * W * (C + N) / 1e9
-    print(f'N={N}: {t:.3f} ms  {gb / t * 1e3:.0f} GB/s  {2.0 * B * H * W * C * N / t / 1e9:.1f} TF/s  (NBM_SHORTK_MAX={os.environ.get("NBM_SHORTK_MAX", "default")})', flush=True)
+    print(f'N={N}: {t:.3f} ms  {gb / t * 1e3:.0f} GB/s  {2.0 * B * H * W * C * N / t / 1e9:.1f} TF/s', flush=True)
 # plain device copy of the same number of bytes for reference
 src = torch.empty(int(4.0 * B * H * W * (C + 384) / 8), device='cuda'); dst = torch.empty_like(src)
 for _ in range(3):

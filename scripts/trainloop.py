@@ -1,6 +1,6 @@
 """Wall time per training step the way bench.py's train leg measures it (no synchronisation inside the loop), alternating blocks
 of steps with a module switch on / off:  python trainloop.py B steps_per_block blocks module.SWITCH [module.SWITCH ...]
-e.g. `trainloop.py 128 4 3 functional.PREMASK`.  Prints the mean step time of every block."""
+e.g. `trainloop.py 128 4 3 functional.LAZY_DGRAD`.  Prints the mean step time of every block."""
 import sys, os, time, importlib, torch, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from birdsoundclassif_amd import synth
