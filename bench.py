@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the NBM detect hot path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch of synthetic input per rank:
@@ -11,10 +11,13 @@ One "step" = one pass of the hot path over one batch of synthetic input per rank
 Workload = BASELINE.json configs[1] (batch 64 per GPU, fp32).  Multi-GPU: clips are independent, every rank
 runs its own batch (weak scaling, no data-path collective); value = all clips of all ranks / max-over-ranks time.
 
-Prints ONE JSON line on rank 0, carrying `roofline` (dominant kernel: the deep-K instantiation of the fp32-MFMA implicit-GEMM
-kernel, all its launches of a step timed live with HIP events on the launch stream), `bulk_inference` (configs[4] on this
-rank's shard: wav files -> txt files end to end), `train_step` (configs[2] / [3]) and `cpu_baseline` (the oracle port on the
-host cores, bounded sample, N=1 only).  `python bench.py --gpus N` starts its N ranks itself (see launch_ranks).
+Prints ONE JSON line on rank 0.  A plain run does what the headline needs and nothing else: the detect leg below, then the
+line.  With `--full` it goes on after the detect leg and the line also carries `roofline` (dominant kernel: the deep-K
+instantiation of the fp32-MFMA implicit-GEMM kernel, all its launches of a step timed live with HIP events on the launch
+stream), `split_bf16` (the opt-in bf16-pipe mode), `frontend`, `dense_finest_map`, `bulk_inference` (configs[4] on this rank's
+shard: wav files -> txt files end to end), `train_step` (configs[2] / [3]) and `cpu_baseline` (the oracle port on the host
+cores, bounded sample, N=1 only); the `--no-*` / `--bulk-files` / `--train-*` options shape those legs.
+`python bench.py --gpus N` starts its N ranks itself (see launch_ranks).
 
 Order of the detect leg: `--spin-up` untimed steps (idle -> steady clocks), W warm-up steps, K eager steps with HIP events around
 the dominant kernel's launches (-> `roofline`, `eager_with_events`), then the same step captured in a hipGraph: W warm-up replays and
@@ -361,6 +364,23 @@ def bulk_bench(model, rank, world, dist, n_files, batch, min_score, headline_cli
         shutil.rmtree(root, ignore_errors=True)
 
 
+def frontend_bench(fe, pcm, B, reps=5):
+    """The front end alone (HBM-bound stage of the path): live HIP events around `reps` calls, the median."""
+    fe_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for s0, e0 in fe_ev:
+        s0.record()
+        fe(pcm, 22050)
+        e0.record()
+    torch.cuda.synchronize()
+    fe_ms = sorted(s0.elapsed_time(e0) for s0, e0 in fe_ev)[len(fe_ev) // 2]
+    fe_flop = 2.0 * 2 * 384 * 664 * 1024            # per clip: Re and Im GEMMs, 384 x 664 x 1024 (bins x k x frames, padded)
+    return {'ms_per_batch': fe_ms, 'clips_per_s': B / fe_ms * 1e3,
+            'hbm_algorithmic_GBps': B * 1.668e6 / (fe_ms * 1e-3) / 1e9, 'hbm_peak_GBps': 8000.0,
+            'dft_gemm_executed_TFLOPs_f64': B * fe_flop / (fe_ms * 1e-3) / 1e12, 'mfma_f64_peak_TFLOPs': FP64_MFMA_PEAK_TFLOPS,
+            'note': 'PCM16 -> 2x up-sample -> STFT-dB (folded real DFT on the fp64 MFMA, csrc/stft.hip) -> normalise/window; '
+                    'algorithmic bytes 1.668 MB/clip (SURVEY 8d); the stage is bound by the DFT-GEMMs, not by HBM'}
+
+
 def cpu_baseline(n_clips=16, batch=4, threads=32, threads8_clips=8):
     """Oracle port (numpy front end + pure-torch detector) on the host cores; bounded sample (~10-20 s).
     32 torch threads: measured fastest on the GPU box (8: 1.36, 16: 1.43, 32: 1.81, 64: 1.13, 128: 0.54 clips/s for
@@ -429,6 +449,10 @@ def parse_args(argv=None):
                     help='detect steps in flight together on one GPU: parallel branches (one stream each) of ONE captured graph '
                          '(bulk.GraphedDetector(lanes=k)): the kernel tails of one step are filled by the other -- 65.2 against 68.9 ms '
                          'per batch (profiles/r04_two_lanes.txt); 1 = one step at a time')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline\'s detect leg, also run the other legs: roofline, split_bf16, frontend, dense_finest_map, '
+                         'bulk_inference, train_step, cpu_baseline (shaped by --no-cpu-baseline, --train-batch, --train-steps, --no-train, '
+                         '--no-dense-reference, --no-split-leg, --bulk-files); off by default: a plain run times the headline only')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--train-batch', type=int, default=128)
     ap.add_argument('--train-steps', type=int, default=8,
@@ -854,7 +878,7 @@ def main(argv=None):
     # through split fp32 operands (x = hi + mid + lo, six products, two fp32 accumulators: csrc/igemm_split.hip; error against float64
     # <= the fp32 instruction's, asserted in tests/test_gpu_split.py).  Single-rank runs only, like the dense leg.
     split_leg = None
-    if world == 1 and not a.no_split_leg and dt_g is not None:
+    if a.full and world == 1 and not a.no_split_leg and dt_g is not None:
         os.environ['NBM_SPLIT_BF16'] = '1'
         try:
             step()
@@ -899,17 +923,19 @@ def main(argv=None):
         finally:
             os.environ['NBM_SPLIT_BF16'] = '0'
             ops.PROFILE, ops.PROFILE_ONLY = None, None
-    ops.PROFILE = []                                           # one extra, untimed step with events around every GEMM-type launch
-    ops.FLOPS = [0.0]                                          # ... and the executed-MFMA-FLOP counter of every GEMM launch
-    step()
-    torch.cuda.synchronize()
-    exec_gflop_per_clip = ops.flops_total() / B / 1e9 + 2.0 * 2 * 384 * 664 * 1024 / 1e9      # + the fp64 DFT GEMMs of the front end
-    prof_all, ops.PROFILE, ops.FLOPS = ops.PROFILE, None, None
+    prof_all, exec_gflop_per_clip = [], None
+    if a.full:
+        ops.PROFILE = []                                       # one extra, untimed step with events around every GEMM-type launch
+        ops.FLOPS = [0.0]                                      # ... and the executed-MFMA-FLOP counter of every GEMM launch
+        step()
+        torch.cuda.synchronize()
+        exec_gflop_per_clip = ops.flops_total() / B / 1e9 + 2.0 * 2 * 384 * 664 * 1024 / 1e9  # + the fp64 DFT GEMMs of the front end
+        prof_all, ops.PROFILE, ops.FLOPS = ops.PROFILE, None, None
     # for the record: the same step with the finest FPN level computed densely, as the reference does -- untimed
     # for the headline, 2 warm-up + 10 steps; single-rank runs only (a failure of this optional leg on one rank must not leave
     # the other ranks in a barrier)
     dense_ref = None
-    if ondemand.LAZY_FINEST and not a.no_dense_reference and world == 1:
+    if a.full and ondemand.LAZY_FINEST and not a.no_dense_reference and world == 1:
         ondemand.LAZY_FINEST = False
         try:
             step()
@@ -946,17 +972,17 @@ def main(argv=None):
     fused_ms = sum(s.elapsed_time(e) for (tag, s, e) in prof_all
                    if len(tag) == 9 and isinstance(tag[8], tuple) and tag[8][0] in ('wino23', 'wino23-rois'))
     roof = None
-    traffic = None                      # HBM bytes per launch of the dominant kernel: PMC counters cannot be read live;
-    traffic_why = None
-    try:                                # the value comes from the committed rocprofv3 --pmc passes of this same command
-        pj = json.load(open(os.path.join(ROOT, 'profiles', PMC_DOMINANT)))
-        if B == 64 and pj.get('lazy_finest') == bool(ondemand.LAZY_FINEST) and pj.get('kernel_family') == 'igemm deep-K':
-            traffic = pj['traffic_bytes_per_launch']
-        else:
-            traffic_why = 'batch / on-demand mode differ from that profile'
-    except Exception as exc:
-        traffic, traffic_why = None, f'profiles/{PMC_DOMINANT} not readable ({type(exc).__name__})'
-    if deep:
+    if a.full and deep:
+        traffic = None                  # HBM bytes per launch of the dominant kernel: PMC counters cannot be read live;
+        traffic_why = None
+        try:                            # the value comes from the committed rocprofv3 --pmc passes of this same command
+            pj = json.load(open(os.path.join(ROOT, 'profiles', PMC_DOMINANT)))
+            if B == 64 and pj.get('lazy_finest') == bool(ondemand.LAZY_FINEST) and pj.get('kernel_family') == 'igemm deep-K':
+                traffic = pj['traffic_bytes_per_launch']
+            else:
+                traffic_why = 'batch / on-demand mode differ from that profile'
+        except Exception as exc:
+            traffic, traffic_why = None, f'profiles/{PMC_DOMINANT} not readable ({type(exc).__name__})'
         per = [(tag, ms, gemm_gflop(tag)) for tag, ms in deep]
         gflop, ms = sum(g for _, _, g in per), sum(m for _, m, _ in per)
         ach = gflop / ms                                       # GFLOP/ms == TFLOP/s
@@ -994,22 +1020,9 @@ def main(argv=None):
                                    'non-GEMM kernel; direct_conv_equivalent uses SURVEY 325.56 GFLOP/clip and is NOT a roofline figure',
                 'fpn_levels_0_1': 'on demand (pattern pixels of the RPN readers through the cell transforms + tiles under the RoIs; the '
                                   'other pixels have no reader)' if ondemand.LAZY_FINEST else 'dense'}
-    # front end alone (HBM-bound stage of the path): live HIP events around K replays
-    fe_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
-    for s0, e0 in fe_ev:
-        s0.record()
-        fe(pcm, 22050)
-        e0.record()
-    torch.cuda.synchronize()
-    fe_ms = sorted(s0.elapsed_time(e0) for s0, e0 in fe_ev)[len(fe_ev) // 2]
-    fe_flop = 2.0 * 2 * 384 * 664 * 1024            # per clip: Re and Im GEMMs, 384 x 664 x 1024 (bins x k x frames, padded)
-    frontend = {'ms_per_batch': fe_ms, 'clips_per_s': B / fe_ms * 1e3,
-                'hbm_algorithmic_GBps': B * 1.668e6 / (fe_ms * 1e-3) / 1e9, 'hbm_peak_GBps': 8000.0,
-                'dft_gemm_executed_TFLOPs_f64': B * fe_flop / (fe_ms * 1e-3) / 1e12, 'mfma_f64_peak_TFLOPs': FP64_MFMA_PEAK_TFLOPS,
-                'note': 'PCM16 -> 2x up-sample -> STFT-dB (folded real DFT on the fp64 MFMA, csrc/stft.hip) -> normalise/window; '
-                        'algorithmic bytes 1.668 MB/clip (SURVEY 8d); the stage is bound by the DFT-GEMMs, not by HBM'}
+    frontend = frontend_bench(fe, pcm, B) if a.full else None
     bulk_leg = None
-    if a.bulk_files > 0:
+    if a.full and a.bulk_files > 0:
         try:
             bulk_leg = bulk_bench(model, rank, world, dist, a.bulk_files, B, a.min_score, B * a.steps / dt, lanes=a.lanes)
         except Exception as exc:                  # never lose the headline line over an extra leg
@@ -1025,7 +1038,7 @@ def main(argv=None):
         elif 'error' not in bulk_leg:
             bulk_leg = {'error': 'the bulk_inference leg failed on another rank'}
     train = None
-    if not a.no_train:
+    if a.full and not a.no_train:
         del model
         import gc
         gc.collect()                              # the captured graphs of the detect / bulk legs own private pools: let them go
@@ -1051,11 +1064,13 @@ def main(argv=None):
                                        'hipGraph replay of the captured step') if dt_g is not None else (graph_note or 'eager loop')),
                            'lanes': lanes_used, 'launch_note': graph_note},
                 'eager_with_events': eager, 'single_lane_graph_replay': single_lane, 'multi_lane_graph_replay': multi_lane,
-                'roofline': roof, 'split_bf16': split_leg, 'frontend': frontend, 'dense_finest_map': dense_ref, 'bulk_inference': bulk_leg,
-                'train_step': train, 'deep_k_gemm': 'fp32 matrix instruction (library default; NBM_SPLIT_BF16 pinned to 0 for every leg but `split_bf16`'
+                'full': a.full, 'deep_k_gemm': 'fp32 matrix instruction (library default; NBM_SPLIT_BF16 pinned to 0 for every leg but `split_bf16`'
                                + (f'; the caller had set it to {split_env_was!r}' if split_env_was not in (None, '0') else '') + ')', **dist_info}
-        if world == 1 and not a.no_cpu_baseline:
-            line['cpu_baseline'] = cpu_baseline()
+        if a.full:                                # the legs of --full: absent from a plain run's line
+            line.update({'roofline': roof, 'split_bf16': split_leg, 'frontend': frontend, 'dense_finest_map': dense_ref,
+                         'bulk_inference': bulk_leg, 'train_step': train})
+            if world == 1 and not a.no_cpu_baseline:
+                line['cpu_baseline'] = cpu_baseline()
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -1,11 +1,15 @@
-"""Prints the main figures of a bench.py JSON line.  usage: python scripts/bench_summary.py file.json"""
+"""Prints the main figures of a bench.py JSON line (the headline alone for a plain run, everything for one with --full).
+usage: python scripts/bench_summary.py file.json"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print('detect', round(d['value'], 1), 'clips/s', round(d['ms_per_step'], 2), 'ms; distinct clips', d['config'].get('distinct_clips'), 'lanes', d['config'].get('lanes'))
-r = d['roofline']
-print('roofline frac', round(r['frac'], 3), 'alg bytes/launch', r.get('algorithmic_bytes_per_launch'), 'traffic', r.get('traffic'), 'wasted', r.get('wasted_traffic_ratio'),
-      'whole-step frac', round(r['whole_step_executed_frac_of_mfma_peak'], 3))
 print('eager', d.get('eager_with_events', {}).get('ms_per_step'), 'single', d.get('single_lane_graph_replay'), 'multi', d.get('multi_lane_graph_replay'))
+if not d.get('full', True):                  # a plain run: the other figures come with bench.py --full
+    sys.exit(0)
+r = d.get('roofline')
+if r:
+    print('roofline frac', round(r['frac'], 3), 'alg bytes/launch', r.get('algorithmic_bytes_per_launch'), 'traffic', r.get('traffic'),
+          'wasted', r.get('wasted_traffic_ratio'), 'whole-step frac', round(r['whole_step_executed_frac_of_mfma_peak'], 3))
 s = d.get('split_bf16')
 print('split detect', None if not s else {k: s.get(k) for k in ('value', 'ms_per_step', 'launch_note')}, None if not s or not s.get('roofline') else round(s['roofline']['frac'], 3))
 b = d.get('bulk_inference')

@@ -8,17 +8,17 @@ cd /tmp && export TMPDIR=/tmp
 python3 $R/scripts/fwdprofile.py 64 > $O/fwd_layers.txt 2>&1
 python3 $R/scripts/fwdprofile.py 64 direct > $O/fwd_layers_direct.txt 2>&1
 python3 $R/scripts/trainlayers.py 128 > $O/train_layers.txt 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-dense-reference > $O/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-dense-reference > $O/bench_under_rocprof.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --no-dense-reference > $O/pmc_$c.log 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --no-dense-reference > $O/pmc_$c.log 2>&1
 done
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_MFMA -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-train --no-dense-reference > $O/pmc_MFMA.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_MFMA -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-train --no-dense-reference > $O/pmc_MFMA.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --pmc $c --output-format csv -d $O/pmc_train_$c -- python3 $R/scripts/trainbench.py 128 2 > $O/pmc_train_$c.log 2>&1
 done
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_train_MFMA -- python3 $R/scripts/trainbench.py 128 2 > $O/pmc_train_MFMA.log 2>&1
-# plain bench line (no profiler attached): the numbers DESIGN.md quotes
-python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+# the full bench line (no profiler attached): the numbers DESIGN.md quotes
+python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 GF=$(python3 -c "import json,sys; print(json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1])['roofline']['executed_GFLOP_per_launch'])")
 # dominant kernels: forward = wino23_fused_kernel, mean over ALL its launches of a step (pairs with its average duration in
 # bench_kernel_stats.csv); backward = the weight-gradient kernel's largest launch

@@ -16,7 +16,7 @@ fi
 if [ $PART = all ] || [ $PART = stats ]; then
   # the detect leg alone (the training forward launches the same kernel templates at B = 128: their durations must not mix into the
   # average that is compared with bench.py's live figure for the dominant kernel)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/dstats -- python3 $R/bench.py $DET --no-train > $O/detect_under_rocprof.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/dstats -- python3 $R/bench.py --full $DET --no-train > $O/detect_under_rocprof.log 2>&1
   find $O/dstats -name "*kernel_stats.csv" -exec cp {} $O/detect_kernel_stats.csv \;
   rm -rf $O/dstats
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/tstats -- python3 $R/scripts/trainbench.py 128 3 > $O/train_under_rocprof.log 2>&1
@@ -25,9 +25,9 @@ if [ $PART = all ] || [ $PART = stats ]; then
 fi
 if [ $PART = all ] || [ $PART = pmc_detect ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --steps 2 --warmup 1 --lanes 1 --no-cpu-baseline --no-train --no-dense-reference --bulk-files 0 > $O/pmc_$c.log 2>&1
+    rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -- python3 $R/bench.py --full --steps 2 --warmup 1 --lanes 1 --no-cpu-baseline --no-train --no-dense-reference --bulk-files 0 > $O/pmc_$c.log 2>&1
   done
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_MFMA -- python3 $R/bench.py --steps 2 --warmup 1 --lanes 1 --no-cpu-baseline --no-train --no-dense-reference --bulk-files 0 > $O/pmc_MFMA.log 2>&1
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_MFMA -- python3 $R/bench.py --full --steps 2 --warmup 1 --lanes 1 --no-cpu-baseline --no-train --no-dense-reference --bulk-files 0 > $O/pmc_MFMA.log 2>&1
 fi
 if [ $PART = all ] || [ $PART = pmc_train ]; then
   for c in FETCH_SIZE WRITE_SIZE; do
@@ -42,8 +42,8 @@ if [ $PART = all ] || [ $PART = pmc_train ]; then
   done
 fi
 if [ $PART = all ] || [ $PART = bench ]; then
-  # plain bench line (no profiler attached): the numbers DESIGN.md quotes
-  python3 $R/bench.py --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
+  # the full bench line (no profiler attached): the numbers DESIGN.md quotes
+  python3 $R/bench.py --full --steps 20 --warmup 3 > $O/bench_default.json 2> $O/bench_default.err
 fi
 if [ $PART = all ] || [ $PART = pmc_detect ]; then
   GF=$(python3 -c "import json,sys; print(json.loads(open('$O/bench_default.json').read().strip().splitlines()[-1])['roofline']['executed_GFLOP_per_launch'])" 2>/dev/null || echo 0)

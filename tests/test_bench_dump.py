@@ -46,3 +46,8 @@ def test_dump_and_steps_arguments():
     assert bench.parse_args([]).dump_outputs is None
     with pytest.raises(SystemExit):
         bench.parse_args(['--steps', '0'])
+
+
+def test_full_is_opt_in():
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(['--full', '--steps', '3']).full is True
