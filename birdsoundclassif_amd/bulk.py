@@ -12,7 +12,7 @@ survivors, RoI count, detections per clip) lives in fixed-capacity device buffer
                     batch i
     writer thread   rows -> the reference's per-file output dictionary (single-window `merge_images`) -> `<wav>.txt`
 
-The clips of a batch are INDEPENDENT (`NbmModel.detect(..., independent=True)`): the reference CLI runs one file per model call
+The clips of a batch are INDEPENDENT (`NbmModel.detect_calls` with `ops.batch_segments(B, 1)`, either head): the reference CLI runs one file per model call
 (nbm_detect.py:24-28 -> run_detection.py:49-55, a 3 s clip is a batch of one window), so the batch-coupled proposal counts of
 the reference's ProposalLayer / nms (min over the batch, layers.py:287, nets_utils.py:236) must not couple files that merely
 share a launch here: every clip is a segment of its own (`ops.batch_segments(B, 1)`) and keeps its own counts, exactly as if it
@@ -32,8 +32,18 @@ import torch
 from .nbm_datasets.prepare_dataset import SpectrogramFrontEnd, read_wav_pcm16
 
 
+def check_head_segment(model, count, flag):
+    """The transformer head's default flavour attends across the images of a model call (`ops.mha_segments`, ACROSS_IMAGES):
+    a call = a segment of a bulk launch holds at most ops.MHA_SMAX images."""
+    from . import ops
+    a = model.args
+    if getattr(a, 'tf_rcnn', False) and not getattr(a, 'tf_pe_qk', False) and count > ops.MHA_SMAX:
+        raise ValueError(f'{flag} = {count}: the transformer head (--tf_rcnn) attends across the images of a model call, '
+                         f'at most {ops.MHA_SMAX} of them')
+
+
 class GraphedDetector:
-    """Captures `front end -> model.detect` for a fixed (batch, n_samples, sample rate) and replays it.
+    """Captures `front end -> model.detect_calls` for a fixed (batch, n_samples, sample rate) and replays it.
 
     `lanes` > 1: ONE graph whose capture forks into that many parallel branches (one stream each, joined before the capture ends),
     every branch a complete detect step on its own static input / outputs and its own persistent scratch (`ops.lane`): a replay
@@ -54,6 +64,8 @@ class GraphedDetector:
         self.fes = [SpectrogramFrontEnd(device) for _ in range(self.lanes)]
         self.fe = self.fes[0]
         self.min_score, self.nms_thresh, self.independent = min_score, nms_thresh, independent
+        if not independent:
+            check_head_segment(model, batch, 'clip batch (--bulk_batch)')
         self.n_img = self.fe.n_images(self.fe.n_frames(n_samples * (2 if sr * 2 == self.fe.FREQ else 1)))
         if self.n_img != 1:
             raise NotImplementedError('GraphedDetector handles clips that fit one 1024-column window (<= 3.06 s)')
@@ -121,8 +133,10 @@ class GraphedDetector:
         ops.release_lane_scratch(keep=tuple(others | {0}))
 
     def _run(self, k=0):
+        from . import ops
         imgs, _ = self.fes[k](self.pcms[k], self.sr)
-        return self.model.detect(imgs[:, 0][:, None].contiguous(), self.nms_thresh, self.min_score, independent=self.independent)
+        segments = ops.batch_segments(self.batch, 1, imgs.device) if self.independent else None
+        return self.model.detect_calls(imgs[:, 0][:, None].contiguous(), segments, self.nms_thresh, self.min_score)
 
     def _run_all(self):
         """Lane 0 on the current (main) stream, every other lane on its side stream between a fork and a join."""
@@ -377,7 +391,7 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
 # =========================================================================== multi-window recordings
 # The per-file driver (`run_detection`) makes one model call per group of `bs` windows of one file.  The recording route runs the
 # same calls as SEGMENTS of one graph-replayed launch of `batch` windows: segment k of a file = its windows [k*bs, (k+1)*bs), the
-# proposal counts coupled within the segment only (`NbmModel.detect(..., segments=...)`), so every window comes out as the
+# proposal counts (and the transformer head's attention) coupled within the segment only (`NbmModel.detect_calls`), so every window comes out as the
 # per-file driver's call computes it, while windows of several files fill one launch.
 
 RECORDING_RATES = (22050, 44100)
@@ -481,7 +495,7 @@ before every replay: a tensor of its own, never one of the shared `ops.batch_seg
         from . import ops
         fe = self.fe
         imgs = ops.spec_windows_table(self.table, fe.H_PIX, fe.W_PIX, fe.HOP_SPECTRO)
-        return self.model.detect(imgs[:, None], self.nms_thresh, self.min_score, segments=self.seg)
+        return self.model.detect_calls(imgs[:, None], self.seg, self.nms_thresh, self.min_score)
 
     def close(self):
         super().close()
@@ -513,6 +527,7 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
         if stats is not None:
             stats.update(files=0, windows=0, replays=0, padded_slots=0, shared_replays=0, rejected=[])
         return []
+    check_head_segment(model, bs, 'windows per model call (--batch)')
     packer = SegmentPacker(batch, bs)
     det = detector or RecordingDetector(model, batch, min_score=min_score)
     own_det = detector is None

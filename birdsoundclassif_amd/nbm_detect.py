@@ -41,8 +41,6 @@ def main(argv=None):
     if groups:
         with open(args.bird_dict, 'r') as f:
             bird_dict = json.load(f)
-    if getattr(config, 'tf_rcnn', False):           # per-image RoI counts are not built for the transformer head
-        rest, groups = sorted(rest + [f for g in groups.values() for f in g]), {}
     for key, group in sorted(groups.items()):
         if len(group) < BULK_MIN_FILES:
             rest.extend(group)
@@ -66,7 +64,7 @@ def main(argv=None):
             continue
         done += len(group)
         print(f'{done} / {len(files)} processed~ (bulk route: {len(group)} clips of {key[1]} samples @ {key[0]} Hz)')
-    if not args.no_bulk and not getattr(config, 'tf_rcnn', False):
+    if not args.no_bulk:
         take, others = bulk.recording_files(sorted(rest))
         if sum(w for _, w in take) >= RECORDINGS_MIN_WINDOWS:
             take = [f for f, _ in take]

@@ -343,11 +343,17 @@ class Transformer_RCNN(nn.Module):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
 
-    def forward_nhwc(self, pool, pe, B, R, n_valid=None):
+    def forward_nhwc(self, pool, pe, B, R, n_valid=None, segments=None):
         """pool, pe: NHWC [B*R,2,2,C]; n_valid: device int32, element 0 = RoIs per image that are real
         (the same count for every image of one model call; pe_qk masks the rest)
-        -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc] softmaxed)."""
+        -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc] softmaxed).
+        `segments` (int32 [2, B] device table, evaluation only): the batch is one model call per segment and `n_valid` holds
+        a count per image (int32 [B], equal within a segment): the attention runs through `ops.mha_segments`, whose valid
+        rows are those of a call on the segment alone bit for bit; rows that are no RoI come out as finite numbers that
+        `ops.rcnn_post` never reads."""
         if torch.is_grad_enabled() and (self.training or pool.requires_grad):
+            if segments is not None:
+                raise NotImplementedError('Transformer_RCNN: a segmented batch is an evaluation geometry (no backward form)')
             return self._forward_train(pool, pe, B, R, n_valid)
         cn, M = pool.shape[-1], B * R
         lin = lambda m: (m.weight.detach(), m.bias.detach())
@@ -371,7 +377,11 @@ class Transformer_RCNN(nn.Module):
             else:
                 qkv = ops.linear(x, w, b)
                 q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
-            a = ops.mha_small(q, k, v, nhead=self.nhead, **geom)
+            if segments is not None:
+                a = ops.mha_segments(q, k, v, R, self.nhead, ops.MHA_ACROSS_ROIS if self.tf_pe_qk else ops.MHA_ACROSS_IMAGES,
+                                     segments, n_valid)
+            else:
+                a = ops.mha_small(q, k, v, nhead=self.nhead, **geom)
             x = ops.layernorm(ops.linear(a, *lin(l.self_attn.out_proj), residual=x), *lin(l.norm1), eps=l.norm1.eps)
             h = ops.linear(x, *lin(l.linear1), act=ff_act)
             x = ops.layernorm(ops.linear(h, *lin(l.linear2), residual=x), *lin(l.norm2), eps=l.norm2.eps)
@@ -425,16 +435,17 @@ class FastRCNN(nn.Module):
         self.roi_pooling = ROIPooling(config)
         self.rcnn = Transformer_RCNN(config) if config.tf_rcnn else RCNN(config)
 
-    def _head(self, pool, pe, rois, n_roi):
+    def _head(self, pool, pe, rois, n_roi, segments=None):
         if self.config.tf_rcnn:
-            return self.rcnn.forward_nhwc(pool, pe, rois.shape[0], rois.shape[1], n_roi)
+            return self.rcnn.forward_nhwc(pool, pe, rois.shape[0], rois.shape[1], n_roi, segments)
         return self.rcnn.forward_nhwc(pool, pe)
 
-    def detect_device(self, fmaps_nhwc, rois, n_roi, nms_thresh=0.3, min_score=0.5):
-        """Sync-free eval path -> (det [B,cap,6] rows {class,x1,y1,x2,y2,score}, n_det int32 [B])."""
+    def detect_device(self, fmaps_nhwc, rois, n_roi, nms_thresh=0.3, min_score=0.5, segments=None):
+        """Sync-free eval path -> (det [B,cap,6] rows {class,x1,y1,x2,y2,score}, n_det int32 [B]).  `segments`: the table
+        the RoI counts were formed with (the transformer head couples tokens by it; the conv head works per RoI)."""
         cfg = self.config
         pool, pe, _ = self.roi_pooling.forward_device(rois, n_roi, fmaps_nhwc)
-        reg, cls = self._head(pool, pe, rois, n_roi)
+        reg, cls = self._head(pool, pe, rois, n_roi, segments)
         return ops.rcnn_post(rois, n_roi, reg, cls, cfg.img_width, cfg.img_height, nms_thresh, min_score,
                              cfg.proposal_number)
 

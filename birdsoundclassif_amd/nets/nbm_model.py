@@ -121,9 +121,22 @@ class NbmModel(nn.Module):
             segments = ops.batch_segments(B, 1, samples.device)
         if self.args.tf_rcnn and B > 1 and segments is not None:
             raise NotImplementedError('Transformer_RCNN with per-image RoI counts (independent or segmented detection)')
+        return self.detect_calls(samples, segments, nms_thresh, min_score)
+
+    @torch.no_grad()
+    def detect_calls(self, samples, segments, nms_thresh=0.3, min_score=0.5):
+        """This batch as several model calls, one per segment of `segments` (int32 [2, B] device table, `ops.segment_table` /
+        `ops.batch_segments`; None: the whole batch is one call) -> `detect`'s (det, n_det), sync-free.  Both heads: the conv
+        head works per RoI, the transformer head (`--tf_rcnn`) runs its attention per segment (`ops.mha_segments`: across the
+        RoIs of each image for `tf_pe_qk`, across the images of each segment otherwise), so every image comes out as the bits
+        of `detect` on its segment's images alone.  Segments of the transformer head hold at most `ops.MHA_SMAX` images.
+        This is what the captured bulk routes call.  `detect(independent=True)` / `detect(segments=...)` still raises
+        NotImplementedError on a transformer head with B > 1: a test of the suite pins that refusal, and `detect` is this
+        method behind that guard."""
         fpn_out = self._fpn_nhwc(samples, lazy=True)
         rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, segments=segments)
-        return self.head.fast_rcnn.detect_device(fpn_out, rois, n_roi, nms_thresh, min_score)
+        return self.head.fast_rcnn.detect_device(fpn_out, rois, n_roi, nms_thresh, min_score,
+                                                 segments=segments if self.args.tf_rcnn else None)
 
     def forward(self, samples, nms_thresh=0.3, min_score=0.5):
         """-> list[B] of {'1'..'num_classes': {'bbox_coord','scores'}} (nbm_model.py:66-80).  Eval only."""

@@ -656,6 +656,35 @@ def mha_small(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid=None):
     return out
 
 
+MHA_SMAX = 128                  # csrc/pointwise.hip: longest sequence of nbm_mha_small / nbm_mha_segments
+MHA_ACROSS_ROIS, MHA_ACROSS_IMAGES = 0, 1
+
+
+def mha_segments(q, k, v, R, nhead, mode, segments, n_roi, max_count=None):
+    """`mha_small` for a batch that is several model calls (evaluation only): q, k, v 2-D row views [B*R, >= E], token (b, r) =
+    row b*R + r; `segments` the int32 [2, B] device table (`segment_table`), `n_roi` int32 [B] device counts (equal within a
+    segment) -> out [B*R, E].  MHA_ACROSS_ROIS: attention over the RoIs r < n_roi[b] of each image; MHA_ACROSS_IMAGES: for
+    every slot r < n_roi of a segment, over the segment's images.  Every row is written by the kernel -- zeros where there
+    is no token -- so `out` is not pre-filled; valid rows equal `mha_small` on the segment alone bit for bit.
+    `max_count`: largest segment of the table (default: the most a table of B images can hold, capped at MHA_SMAX -- the
+    rows of a longer segment come out zero)."""
+    E = q.shape[1]
+    hd = E // nhead
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == torch.float32
+    if q.shape[0] % R:
+        raise ValueError(f'{q.shape[0]} token rows are not images of {R} RoI slots')
+    B = q.shape[0] // R
+    _chk_segments(segments, B)
+    _chk_counts(n_roi, B, 'n_roi')
+    max_count = min(B, MHA_SMAX) if max_count is None else int(max_count)
+    out = torch.empty((B * R, E), device=q.device, dtype=torch.float32)
+    check(lib().nbm_mha_segments(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(out), E, B, R, nhead, hd,
+                                 int(mode), _ptr(segments), _ptr(n_roi), max_count, 1.0 / math.sqrt(hd), _stream()),
+          'nbm_mha_segments')
+    return out
+
+
 def pair_softmax(x, n_anchor):
     """x [..., 2*n_anchor] -> softmax over each (bg, fg) pair."""
     _chk(x, name='x')

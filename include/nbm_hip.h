@@ -374,6 +374,21 @@ int nbm_mha_small(const float* q, const float* k, const float* v, int q_ld, int 
                   int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                   float scale, void* stream);
 
+/* nbm_mha_small for a batch that is several model calls (evaluation only, no backward form): token (b, r) is row b*R + r of
+ * q/k/v/out, `segments` the int32 [2][B] table of nbm_rpn_select (first image and image count of b's segment), n_roi[b] the RoI
+ * count of image b (equal within a segment).  ACROSS_ROIS (tf_pe_qk): per image, keys and queries r < n_roi[b]; `segments` is
+ * not read.  ACROSS_IMAGES (default flavour, batch_first=False): per segment and slot r < n_roi[first], the sequence is the
+ * segment's images.  EVERY row of `out` is written: rows that are no valid token (r >= n_roi, failed segments) are zero, so
+ * the caller need not pre-fill.  A valid row holds the bits nbm_mha_small gives when it is run on that row's segment alone.
+ * max_count: the caller's bound on the table's segment counts (<= 128); the rows of a segment above it, or of an entry that
+ * is no segment inside [0, B), are zero -- the per-segment model calls of the reference CLI (run_detection.py:49-55) through
+ * layers.py:613-621,645-646. */
+#define NBM_MHA_ACROSS_ROIS 0
+#define NBM_MHA_ACROSS_IMAGES 1
+int nbm_mha_segments(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
+                     int B, int R, int nhead, int hd, int mode, const int32_t* segments, const int32_t* n_roi, int max_count,
+                     float scale, void* stream);
+
 /* softmax over the (bg, fg) pair of every anchor: x[p][2a], x[p][2a+1] (pitch ld) -> y (pitch y_ld)
  * -- layers.py:90. */
 int nbm_pair_softmax(const float* x, int64_t n_pix, int n_anchor, int x_ld, float* y, int y_ld, void* stream);
