@@ -6,7 +6,10 @@ survivors, RoI count, detections per clip) lives in fixed-capacity device buffer
 
 `detect_files` is a three-stage software pipeline around the graph, so that the GPU never waits for a file or a dict:
 
-    reader thread   wav files -> rows of a pinned int16 batch buffer (a ring of `depth` slots)
+    reader thread   wav files -> rows of a pinned batch buffer (a ring of `depth` slots): int16 samples for mono 16-bit PCM at
+                    22.05 / 44.1 kHz, the undecoded payload bytes for every other format (`read_payload`); those are decoded on
+                    the GPU inside the captured step (`ops.wav_decode`: 8- / 16- / 24- / 32-bit PCM, 32- / 64-bit float, up to 8
+                    channels, any rate the resampler takes), bit for bit what `read_wav` gives the per-file driver
     main thread     H2D copy of the slot -> graph replay -> D2H copy of the compact [B,50,6] detection rows + counts into the
                     slot's pinned result buffers, all on the graph's stream; batch i+1 is queued before the host waits for
                     batch i
@@ -29,7 +32,7 @@ import time
 import numpy as np
 import torch
 
-from .nbm_datasets.prepare_dataset import SpectrogramFrontEnd, read_wav_pcm16
+from .nbm_datasets.prepare_dataset import SpectrogramFrontEnd, read_wav_pcm16, resample_ratio, resample_table_size
 
 
 def check_head_segment(model, count, flag):
@@ -58,18 +61,27 @@ class GraphedDetector:
     The persistent scratch / tile-list buffers of the lanes are held as captured (`self._held`), so no later growth or release can
     recycle memory this graph writes to.  Several detectors may be alive at a time (`tests/test_gpu_detect_cli.py`)."""
 
-    def __init__(self, model, batch, n_samples, sr, min_score=0.2, nms_thresh=0.3, device='cuda', independent=False, lanes=1):
+    def __init__(self, model, batch, n_samples, sr, min_score=0.2, nms_thresh=0.3, device='cuda', independent=False, lanes=1,
+                 fmt=None):
+        """`fmt` = (format tag, bits, channels) of the clips' payload (`wav_header`): the static inputs `pcms` are then uint8
+        [batch, row bytes rounded up to 16] batches of raw payload rows, and `ops.wav_decode` + the float front end (resampler
+        for any rate but 44.1 kHz) are captured in front of the detector.  None = mono 16-bit PCM given as int16 samples."""
         from . import ops
         self.model, self.batch, self.sr, self.lanes = model.eval(), batch, sr, max(1, int(lanes))
+        self.fmt, self.n_samples = (tuple(int(v) for v in fmt) if fmt is not None else None), int(n_samples)
+        if self.fmt is not None and not decodable(*self.fmt):
+            raise NotImplementedError(f'wav format tag {fmt[0]} with {fmt[1]} bits per sample and {fmt[2]} channels')
         self.fes = [SpectrogramFrontEnd(device) for _ in range(self.lanes)]
         self.fe = self.fes[0]
         self.min_score, self.nms_thresh, self.independent = min_score, nms_thresh, independent
         if not independent:
             check_head_segment(model, batch, 'clip batch (--bulk_batch)')
-        self.n_img = self.fe.n_images(self.fe.n_frames(n_samples * (2 if sr * 2 == self.fe.FREQ else 1)))
+        self.n44 = n_samples * (2 if sr * 2 == self.fe.FREQ else 1) if fmt is None else samples_44k(sr, n_samples)
+        self.n_img = self.fe.n_images(self.fe.n_frames(self.n44))
         if self.n_img != 1:
             raise NotImplementedError('GraphedDetector handles clips that fit one 1024-column window (<= 3.06 s)')
-        self.pcms = [torch.zeros((batch, n_samples), dtype=torch.int16, device=device) for _ in range(self.lanes)]   # static graph inputs
+        shape, dtype = ((batch, n_samples), torch.int16) if fmt is None else ((batch, payload_pitch(self.fmt, n_samples)), torch.uint8)
+        self.pcms = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(self.lanes)]   # static graph inputs
         self.pcm = self.pcms[0]
         self.stream = torch.cuda.Stream()
         self.side = [torch.cuda.Stream() for _ in range(self.lanes - 1)]
@@ -134,7 +146,8 @@ class GraphedDetector:
 
     def _run(self, k=0):
         from . import ops
-        imgs, _ = self.fes[k](self.pcms[k], self.sr)
+        x = self.pcms[k] if self.fmt is None else ops.wav_decode(self.pcms[k], *self.fmt, self.n_samples)
+        imgs, _ = self.fes[k](x, self.sr)
         segments = ops.batch_segments(self.batch, 1, imgs.device) if self.independent else None
         return self.model.detect_calls(imgs[:, 0][:, None].contiguous(), segments, self.nms_thresh, self.min_score)
 
@@ -191,6 +204,91 @@ def wav_header(path):
                 return tag, nch, sr, bits, size // max(1, nch * (bits // 8)), off
             else:
                 f.seek(size + (size & 1), 1)
+
+
+def decodable(tag, bits, channels):
+    """Does the device decoder (`ops.wav_decode`) take this payload format?  Everything `read_wav` reads, up to 8 channels."""
+    from . import ops
+    return (tag, bits) in ops.WAV_FORMATS and 1 <= channels <= ops.WAV_MAX_CHANNELS
+
+
+def is_pcm16_mono(fmt, sr):
+    """The format with an exact-integer front end of its own (`nbm_pcm16_to_wave`): its payload IS the int16 sample row."""
+    return tuple(fmt) == (1, 16, 1) and sr in RECORDING_RATES
+
+
+def payload_pitch(fmt, n):
+    """Bytes of a payload row of n frames, rounded up to the 16 bytes the decoder wants between the rows of a batch."""
+    return -(-n * fmt[2] * (fmt[1] // 8) // 16) * 16
+
+
+MAX_RESAMPLE_TABLE = 1 << 23      # taps (float64) of a resampler table the routes are willing to build: 64 MiB
+
+
+def samples_44k(sr, n):
+    """Length of the 44.1 kHz signal the front end makes of n samples at `sr` (SpectrogramFrontEnd._source): n L / M rounded
+    up, L / M = 44100 / sr reduced -- n for 44.1 kHz, 2 n for 22.05 kHz."""
+    L, M = resample_ratio(sr, SpectrogramFrontEnd.FREQ)
+    return -(-n * L // M)
+
+
+def rate_ok(sr):
+    """A rate whose polyphase table (`resample_taps`) is of a sane size."""
+    return sr >= 1 and resample_table_size(sr, SpectrogramFrontEnd.FREQ) <= MAX_RESAMPLE_TABLE
+
+
+# the front end's default geometry (SpectrogramFrontEnd(dt=0.003, w_pix=1024)), which both routes and the CLI run with
+HOP_LENGTH, W_PIX = int(SpectrogramFrontEnd.FREQ * 0.003), 1024
+
+
+def single_window(n44):
+    """Does a 44.1 kHz signal of n44 samples fill exactly one spectrogram window (prepare_dataset.py:126,267)?"""
+    return 1 + n44 // HOP_LENGTH <= W_PIX
+
+
+def read_payload(path, out=None):
+    """The sample bytes of a wav file, undecoded: -> ((tag, bits, channels), sample rate, frames, uint8 buffer [frames * frame
+    bytes]).  The chunk headers are parsed (`wav_header`) and the payload is read straight into `out` (a writable uint8 numpy
+    array, e.g. a row of a pinned batch; it must be large enough) or, by default, into a fresh pinned tensor, whose numpy
+    view is returned -- no decode, no per-sample work.  A truncated payload gives its whole frames, like `read_wav`."""
+    tag, nch, sr, bits, n, off = wav_header(path)
+    if not decodable(tag, bits, nch):
+        raise NotImplementedError(f'{path}: wav format tag {tag} with {bits} bits per sample and {nch} channels')
+    nbytes = n * nch * (bits // 8)
+    if out is None:
+        pin = torch.empty((max(1, nbytes),), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+        out = pin.numpy()
+    if out.dtype != np.uint8 or out.ndim != 1 or len(out) < nbytes:
+        raise ValueError(f'{path}: a payload of {nbytes} bytes does not fit the buffer')
+    with open(path, 'rb', buffering=0) as f:
+        f.seek(off)
+        got, view = 0, memoryview(out)[:nbytes]
+        while got < nbytes:
+            k = f.readinto(view[got:])
+            if not k:
+                raise ValueError(f'{path}: the file shrank while it was read')
+            got += k
+    return (tag, bits, nch), sr, n, out[:nbytes]
+
+
+def format_groups(files):
+    """`bulk_groups` for every format the device decoder takes: {(tag, bits, channels, sample rate, frames): [files]} of the
+    clips whose 44.1 kHz signal fills exactly one spectrogram window, and the rest.  Applied to what `bulk_groups` leaves
+    over it yields the clip groups of the other formats (mono PCM16 at 22.05 / 44.1 kHz keeps its own route)."""
+    groups, rest = {}, []
+    for f in files:
+        try:
+            tag, nch, sr, bits, n, _ = wav_header(f)
+        except (OSError, ValueError, struct.error):
+            rest.append(f)
+            continue
+        ok = decodable(tag, bits, nch) and n > 0 and rate_ok(sr)
+        ok = ok and single_window(samples_44k(sr, n))
+        if ok:
+            groups.setdefault((tag, bits, nch, sr, n), []).append(f)
+        else:
+            rest.append(f)
+    return groups, rest
 
 
 def bulk_groups(files):
@@ -254,7 +352,8 @@ def txt_path(wav_path):
 
 def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_txt=True, depth=5, keep_results=True,
                  independent=True, stats=None, detector=None, lanes=None):
-    """Detects over equal-length mono 16-bit PCM wav files (single-window clips, see `bulk_groups`): -> list of per-file output
+    """Detects over equal-length wav files of one format and rate (single-window clips, see `bulk_groups` for mono 16-bit PCM
+    at 22.05 / 44.1 kHz and `format_groups` for everything else the device decoder takes): -> list of per-file output
     dicts in `files` order (None entries with keep_results=False); `<wav>.txt = str(dict)` written when `write_txt`.
     The last, partial batch is padded with silence and its padding results are dropped.  `stats` (dict) receives the stage
     times.  `detector`: a GraphedDetector to reuse (same batch / clip length / rate / lanes).
@@ -262,24 +361,28 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
     in groups of that many, in flight on the GPU together (see GraphedDetector)."""
     if not files:
         return []
-    _, _, sr, _, n, _ = wav_header(files[0])
+    tag, nch, sr, bits, n, _ = wav_header(files[0])
+    fmt = None if is_pcm16_mono((tag, bits, nch), sr) else (tag, bits, nch)     # None: the int16 samples themselves
     n_batches = -(-len(files) // batch)
     if lanes is None:
         lanes = detector.lanes if detector is not None else int(os.environ.get('NBM_BULK_LANES', '2' if n_batches >= 4 else '1'))
     lanes = max(1, int(lanes))
-    det = detector or GraphedDetector(model, batch, n, sr, min_score=min_score, independent=independent, lanes=lanes)
+    det = detector or GraphedDetector(model, batch, n, sr, min_score=min_score, independent=independent, lanes=lanes, fmt=fmt)
     own_det = detector is None
-    if (det.batch, det.pcm.shape[1], det.sr) != (batch, n, sr) or det.lanes != lanes:
-        raise ValueError('the GraphedDetector handed in was captured for another batch / clip length / sample rate / number of lanes')
+    if (det.batch, det.n_samples, det.sr, det.fmt) != (batch, n, sr, fmt) or det.lanes != lanes:
+        if own_det:
+            det.close()
+        raise ValueError('the GraphedDetector handed in was captured for another batch / clip length / sample rate / format / '
+                         'number of lanes')
     fe = det.fe
-    L = fe.n_frames(n * (2 if sr * 2 == fe.FREQ else 1))
+    L = fe.n_frames(det.n44)
     names = None
     if bird_dict is not None:
         names = {v: k for k, v in bird_dict.items()}
         names[0] = 'Non bird sound'
     depth = max(3, depth, 3 * lanes)
     cap = det.det.shape[1]
-    slots = [(torch.zeros((batch, n), dtype=torch.int16).pin_memory(), torch.zeros((batch, cap, 6), dtype=torch.float32).pin_memory(),
+    slots = [(torch.zeros(det.pcm.shape, dtype=det.pcm.dtype).pin_memory(), torch.zeros((batch, cap, 6), dtype=torch.float32).pin_memory(),
               torch.zeros((batch,), dtype=torch.int32).pin_memory()) for _ in range(depth)]
     free_q, ready_q, done_q = queue.Queue(), queue.Queue(), queue.Queue()
     for s in range(depth):
@@ -299,10 +402,14 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
                 chunk = files[i * batch:(i + 1) * batch]
                 host = slots[s][0].numpy()
                 for j, f in enumerate(chunk):
-                    p, sr_i = read_wav_pcm16(f)
-                    if sr_i != sr or len(p) != n:
-                        raise ValueError(f'{f}: bulk detection needs clips of identical length and rate')
-                    host[j] = p
+                    if fmt is None:
+                        p, sr_i = read_wav_pcm16(f)
+                        if sr_i != sr or len(p) != n:
+                            raise ValueError(f'{f}: bulk detection needs clips of identical length and rate')
+                        host[j] = p
+                    else:                            # the payload bytes, undecoded, straight into the pinned row
+                        if read_payload(f, host[j])[:3] != (fmt, sr, n):
+                            raise ValueError(f'{f}: bulk detection needs clips of identical format, length and rate')
                 if len(chunk) < batch:
                     host[len(chunk):] = 0
                 t_read[0] += time.perf_counter() - t0
@@ -398,9 +505,9 @@ RECORDING_RATES = (22050, 44100)
 
 
 def recording_windows(sr, n, w_pix=1024, hop_img=819, hop=int(44100 * 0.003), max_chunk=int(5e7)):
-    """Number of spectrogram windows of a mono file of n samples at `sr` (prepare_dataset.py:267, per-chunk frame counts of the
-    STFT above 5e7 samples like SpectrogramFrontEnd.spectrogram_db)."""
-    n44 = n * (2 if sr * 2 == 44100 else 1)
+    """Number of spectrogram windows of a file of n samples per channel at any rate `sr` (prepare_dataset.py:267, per-chunk
+    frame counts of the STFT above 5e7 samples of the 44.1 kHz signal like SpectrogramFrontEnd.spectrogram_db)."""
+    n44 = samples_44k(sr, n)
     if n44 < max_chunk:
         L = 1 + n44 // hop
     else:
@@ -422,6 +529,25 @@ def recording_files(files):
             continue
         n44 = n * (2 if sr == 22050 else 1)
         if tag == 1 and nch == 1 and bits == 16 and sr in RECORDING_RATES and 0 < n44 <= max_l:
+            take.append((f, recording_windows(sr, n)))
+        else:
+            rest.append(f)
+    return take, rest
+
+
+def decodable_recordings(files):
+    """`recording_files` for every format the device decoder takes, at any sample rate: [(file, windows)] of the files whose
+    44.1 kHz signal is not longer than the same limit, and the rest (compressed formats, more than 8 channels, unreadable
+    headers, longer files).  Applied to what `recording_files` leaves over it yields the recordings of the other formats."""
+    take, rest = [], []
+    max_l = int(15e7) - int(15e7) % 44100
+    for f in files:
+        try:
+            tag, nch, sr, bits, n, _ = wav_header(f)
+        except (OSError, ValueError, struct.error):
+            rest.append(f)
+            continue
+        if decodable(tag, bits, nch) and rate_ok(sr) and n > 0 and samples_44k(sr, n) <= max_l:
             take.append((f, recording_windows(sr, n)))
         else:
             rest.append(f)
@@ -502,25 +628,34 @@ before every replay: a tensor of its own, never one of the shared `ops.batch_seg
         self.table = self.seg = None
 
 
+# Payload bytes the reader of the recording route may have read and not yet handed to the main thread.  A limit on reading
+# ahead, not on pinned memory: a buffer the main thread has taken stays busy until its queued H2D copy has run (the main thread
+# is at most 3 replays ahead of the GPU), and torch's host allocator keeps freed pinned blocks for reuse.
+RECORDING_AHEAD_BYTES = 4 << 30
+
+
 def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=None, write_txt=True, keep_results=True,
-                      stats=None, detector=None, depth=4):
-    """Detects over mono 16-bit PCM recordings of any number of windows (`recording_files`) through one captured graph:
+                      stats=None, detector=None, depth=4, ahead_bytes=RECORDING_AHEAD_BYTES):
+    """Detects over recordings of any number of windows, in any format the device decoder takes and at any sample rate
+    (`recording_files`, `decodable_recordings`), through one captured graph:
     -> list of per-file output dicts in `files` order, each exactly `run_detection(model, cfg, f, ..., bs=bs)`'s (None for
     keep_results=False and for rejected files); `<wav>.txt = str(dict)` written when `write_txt`.
 
-        reader thread   wav -> pinned int16 buffer                     (at most `depth` files ahead)
-        main thread     per file: H2D, spectrogram_db + column map on the graph's stream; its segments go to the SegmentPacker;
+        reader thread   wav payload bytes -> pinned uint8 buffer, undecoded (`read_payload`; at most `depth` files and
+                        `ahead_bytes` bytes ahead of the main thread, one file always allowed)
+        main thread     per file: H2D of the bytes, `ops.wav_decode` (mono PCM16 at 22.05 / 44.1 kHz: the bytes ARE the int16
+                        row of the exact-integer front end), spectrogram_db + column map on the graph's stream; its segments go
+                        to the SegmentPacker;
                         per full replay: window / segment tables H2D -> replay -> the slots' rows D2D into each file's row
                         buffer; per finished file: merge_device_async + D2H into pinned memory, an event behind it
         writer thread   waits for a file's event -> dict -> txt
 
     Everything the GPU does runs on one stream in issue order, so a dB plane or row buffer released by the host after its
     last use is only handed out again to work queued behind that use.  At most 3 replays are in flight.
-    A file the reader cannot decode as mono PCM16 at 22.05 / 44.1 kHz (or whose front end refuses it) is skipped and listed in
-    stats['rejected'] for the per-file driver.  `stats` (dict) also receives counts and stage times.  `detector`: a
+    A file whose format the decoder does not take (or whose front end refuses it, e.g. for its length) is skipped and listed
+    in stats['rejected'] for the per-file driver.  `stats` (dict) also receives counts and stage times.  `detector`: a
     RecordingDetector to reuse (same batch / min_score)."""
     from . import ops
-    from .nbm_datasets.prepare_dataset import read_wav_pcm16
     from .run_detection import merge_device_async, rows_to_output, species_names
     from types import SimpleNamespace
     if not files:
@@ -540,6 +675,8 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
     read_q, done_q = queue.Queue(maxsize=max(1, depth)), queue.Queue()
     t_read, t_write = [0.0], [0.0]
     stop = threading.Event()
+    room = threading.Condition()
+    held = [0]                                     # payload bytes read and not yet taken over by the main thread
 
     def reader():
         try:
@@ -548,17 +685,35 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
                     break
                 t0 = time.perf_counter()
                 try:
-                    x, sr = read_wav_pcm16(f)
-                    if sr not in RECORDING_RATES or len(x) == 0:
-                        raise ValueError(f'{f}: {sr} Hz / {len(x)} samples is not a recording the route takes')
-                    pin = torch.empty((1, len(x)), dtype=torch.int16, pin_memory=True)
-                    pin.numpy()[0] = x
+                    tag, nch, sr, bits, n, _ = wav_header(f)
+                    if not decodable(tag, bits, nch) or not rate_ok(sr) or n == 0:
+                        raise ValueError(f'{f}: format tag {tag}, {bits} bits, {nch} channels, {sr} Hz, {n} frames is not a '
+                                         'recording the route takes')
+                    nbytes = n * nch * (bits // 8)
+                    t_read[0] += time.perf_counter() - t0
+                    with room:                     # one file may always be held, whatever its size
+                        while held[0] and held[0] + nbytes > ahead_bytes and not stop.is_set():
+                            room.wait(0.05)
+                        held[0] += nbytes
+                    t0 = time.perf_counter()
+                    try:
+                        try:
+                            pin = torch.empty((1, nbytes), dtype=torch.uint8, pin_memory=True)
+                        except RuntimeError as exc:           # no pinned memory of that size: the per-file driver reads the file
+                            raise OSError(f'{f}: {exc}') from None
+                        fmt, sr, n, _ = read_payload(f, pin.numpy()[0])
+                        if n * fmt[2] * (fmt[1] // 8) != nbytes:
+                            raise ValueError(f'{f}: the file changed while it was read')
+                    except BaseException:
+                        with room:
+                            held[0] -= nbytes
+                        raise
                 except (OSError, ValueError, NotImplementedError, struct.error):
                     rejected.append(f)
                     continue
                 finally:
                     t_read[0] += time.perf_counter() - t0
-                read_q.put((i, pin, sr))
+                read_q.put((i, pin, fmt, sr, n))
         except BaseException as exc:                 # noqa: BLE001 -- handed to the main thread
             err.append(exc)
         finally:
@@ -638,10 +793,18 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
                 t_wait += time.perf_counter() - t0
                 if item is None:
                     break
-                i, pin, sr = item
+                i, pin, fmt, sr, n = item
                 t0 = time.perf_counter()
+                raw = pin.to('cuda', non_blocking=True)
+                with room:
+                    held[0] -= pin.shape[1]
+                    room.notify()
+                del pin
                 try:
-                    db, mm, Ls = fe.spectrogram_db(pin.to('cuda', non_blocking=True), sr)
+                    x = raw.view(torch.int16) if is_pcm16_mono(fmt, sr) else ops.wav_decode(raw, *fmt, n)
+                    del raw
+                    db, mm, Ls = fe.spectrogram_db(x, sr)
+                    del x
                 except (ValueError, NotImplementedError):      # e.g. a length the reference's chunked STFT fails on
                     rejected.append(files[i])
                     continue

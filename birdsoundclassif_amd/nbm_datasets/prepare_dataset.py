@@ -207,15 +207,26 @@ RESAMPLE_ZEROS = 16          # zero crossings of the windowed sinc on each side
 RESAMPLE_ROLLOFF = 0.95
 
 
+def resample_ratio(sr, target=44100):
+    """target / sr = L / M reduced."""
+    from math import gcd
+    g = gcd(int(sr), int(target))
+    return int(target) // g, int(sr) // g
+
+
+def resample_table_size(sr, target=44100):
+    """Number of taps (float64) of the table `resample_taps(sr, target)` builds, without building it."""
+    L, M = resample_ratio(sr, target)
+    return L * 2 * int(np.ceil(RESAMPLE_ZEROS / min(1.0, L / M)))
+
+
 def resample_taps(sr, target=44100):
     """Polyphase taps of the rational resampler sr -> target (reference: `ffmpeg -ar 44100`, prepare_dataset.py:175-178,
     third-party and absent; this build owns the filter): target / sr = L / M reduced, y[m] = sum_n x[n] g(m M / L - n) with
     g(tau) = rho s sinc(rho s tau) kaiser_8(tau s / 16), s = min(1, L / M), rho = 0.95, |tau| < 16 / s.  Returns
     (L, M, float64 [L, T]): row `ph` holds the taps of output phase ph for the inputs floor(m M / L) - T/2 + 1 + k,
     k = 0 .. T-1, each row normalised to unit DC gain."""
-    from math import gcd
-    g = gcd(int(sr), int(target))
-    L, M = int(target) // g, int(sr) // g
+    L, M = resample_ratio(sr, target)
     sc = min(1.0, L / M)
     half = int(np.ceil(RESAMPLE_ZEROS / sc))
     T = 2 * half

@@ -417,6 +417,35 @@ def pcm16_to_wave(pcm, out_ld, lead, upsample, hq=None, reflect=False, first=0, 
     return out
 
 
+WAV_FORMATS = ((1, 8), (1, 16), (1, 24), (1, 32), (3, 32), (3, 64))      # (resolved format tag, bits) nbm_wav_decode takes
+WAV_MAX_CHANNELS = 8
+
+
+def wav_decode(raw, tag, bits, channels, n, out=None):
+    """raw uint8 [batch, pitch] (device; every row the interleaved sample bytes of a wav `data` payload, n frames) ->
+    f32 [batch, n] mono samples, bit for bit what `prepare_dataset.read_wav` returns for those bytes.  `tag` is the
+    resolved format tag (`bulk.wav_header`).  `out`: f32 rows to write into (unit stride along a row, row pitch >= n;
+    what lies behind the n samples of a row is left alone)."""
+    if not (isinstance(raw, torch.Tensor) and raw.is_cuda):
+        raise RuntimeError('raw: the NBM HIP path needs CUDA (ROCm) tensors; no CPU fallback exists')
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.stride(1) != 1:
+        raise TypeError('raw: expected uint8 [batch, pitch] rows with unit stride')
+    if (int(tag), int(bits)) not in WAV_FORMATS or not 1 <= channels <= WAV_MAX_CHANNELS:
+        raise NotImplementedError(f'wav format tag {tag} with {bits} bits per sample and {channels} channels')
+    batch = raw.shape[0]
+    if n < 1 or n * channels * (bits // 8) > raw.shape[1]:
+        raise ValueError(f'{n} frames do not fit rows of {raw.shape[1]} bytes')
+    if out is None:
+        out = torch.empty((batch, n), device=raw.device, dtype=torch.float32)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.shape[0] == batch and out.shape[1] >= n
+              and out.stride(1) == 1):
+        raise TypeError('out: expected f32 [batch, >= n] rows with unit stride on the device')
+    check(lib().nbm_wav_decode(_ptr(raw), raw.stride(0) if batch > 1 else raw.shape[1], batch, int(tag), int(bits),
+                               int(channels), int(n), _ptr(out), out.stride(0) if batch > 1 else out.shape[1], _stream()),
+          'nbm_wav_decode')
+    return out[:, :n]
+
+
 def resample_to_wave(x, out_ld, lead, L, M, taps, reflect=False, first=0, count=None, quant16=True):
     """x f32 [batch, n] at any rate -> f32 [batch, out_ld] laid out like `pcm16_to_wave`: the piece [first, first+count)
     of the 44.1 kHz signal = x itself (L = M = 1) or its rational L / M polyphase resampling with the float64 `taps`

@@ -270,6 +270,23 @@ int nbm_resample_to_wave(const float* x, int64_t x_ld, int batch, int64_t n, int
                          int64_t first, int64_t count, float* out, int64_t out_ld, int lead, int pad_mode, int quant16,
                          void* stream);
 
+/* Wav payload decoder: the interleaved little-endian sample bytes of `batch` RIFF/WAVE `data` payloads (row b at raw +
+ * b * raw_pitch BYTES, n frames of `channels` samples each) -> mono float32 rows out[b][0 .. n) (row pitch out_pitch
+ * ELEMENTS; nothing else of a row is written).  Replaces the host decode of File_Processor.load (librosa.load(sr=None,
+ * mono=True), prepare_dataset.py:162 = prepare_dataset.read_wav here) in front of nbm_resample_to_wave on the bulk routes
+ * (bulk.detect_files, bulk.detect_recordings), bit for bit:
+ *   (tag, bits) = (1, 8): (u8 - 128) / 128; (1, 16), (1, 24): i / 2^(bits-1); (1, 32): (float)i32 to nearest even, * 2^-31;
+ *   (3, 32): the float itself (one channel: its bits, NaN payloads included); (3, 64): rounded to nearest even;
+ *   channels 2 .. NBM_WAV_MAX_CHANNELS: float32 sum in numpy's order (left to right up to 7 channels, pairwise
+ *   ((0+1)+(2+3))+((4+5)+(6+7)) for 8), one correctly rounded division by the channel count.
+ * `tag` is the resolved format tag (WAVE_FORMAT_EXTENSIBLE 0xFFFE -> the first 16 bits of its sub-format GUID).  Any other
+ * (tag, bits) or channel count: NBM_EUNSUPPORTED.  raw must be 16-byte aligned, and raw_pitch a multiple of 16 when
+ * batch > 1 (NBM_EALIGN); raw_pitch >= n * frame bytes, out_pitch >= n.  All offsets are 64-bit.  One kernel launch on
+ * `stream`, nothing else (capturable). */
+#define NBM_WAV_MAX_CHANNELS 8
+int nbm_wav_decode(const void* raw, int64_t raw_pitch, int batch, int tag, int bits, int channels, int64_t n, float* out,
+                   int64_t out_pitch, void* stream);
+
 /* STFT magnitude in dB for n_bins bins on the fp64 MFMA (librosa.stft + np.abs + amp_to_db + crop,
  * prepare_dataset.py:228-247):
  *   db[b][f][t] = 20 log10(max(floor, | sum_n w[n] wave[b][t*hop + n] exp(-2 pi i (low_bin + f) n / n_fft) |))
