@@ -92,6 +92,7 @@ SIGNATURES = {
     'nbm_mha_segments': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P],
     'nbm_pair_softmax': [_P, _L, _I, _I, _P, _I, _P],
     'nbm_rpn_decode': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    'nbm_nan_images': [_P, _I, _L, _P, _P],
     'nbm_rpn_select': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     'nbm_nms_batched': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
     'nbm_roi_pool': [C.POINTER(RoiDesc), _P],

@@ -58,6 +58,22 @@ __global__ void rpn_decode_kernel(const float* __restrict__ cls, const float* __
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(keep_count + b, __popcll(m));
 }
 
+// An input image that holds a NaN keeps no anchor.  In the reference a NaN pixel spreads through every layer (relu(NaN) and
+// max-pooling keep it; in the default configuration the attention levels and the top-down path carry it to every position:
+// checked with one NaN pixel on the CPU oracle, tests/test_gpu_detect_edges.py), so every comparison of the
+// size filter is false and the image's kept count is 0 ("RPN failed").  The epilogues here clamp with v_max, which drops a
+// NaN, so the decision is taken from the image itself: launched after rpn_decode_kernel on the same stream.
+__global__ void nan_images_kernel(const float* __restrict__ img, long long n, int* __restrict__ keep_count) {
+  const int b = blockIdx.y;
+  const float* p = img + (long long)b * n;
+  bool bad = false;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float v = p[i];
+    bad = bad || (v != v);
+  }
+  if (bad) keep_count[b] = 0;                    // benign race: every writer stores 0
+}
+
 // Segment of image b in a table of contiguous segments: seg[b] = first image, seg[B + b] = image count.  Clamped into
 // [0, B) with b inside it, so that a malformed table can never make a kernel read past the batch.
 __device__ __forceinline__ void seg_range(const int* __restrict__ seg, int B, int b, int& lo, int& hi) {
@@ -596,6 +612,14 @@ extern "C" int nbm_rpn_decode(const float* cls, const float* reg, const float* a
   dim3 grid((KA + 255) / 256, B);
   hipLaunchKernelGGL(rpn_decode_kernel, grid, dim3(256), 0, st, cls, reg, anchors, KA, n_anchor, img_w, img_h,
                      (float)min_size, boxes, keys, keep_count);
+  return nbm_launch_status();
+}
+
+extern "C" int nbm_nan_images(const float* img, int B, int64_t n, int* keep_count, void* stream) {
+  if (!img || !keep_count || B <= 0 || B > 65535 || n <= 0) return NBM_EINVAL;
+  const long long blocks = (n + 1023) / 1024;
+  hipLaunchKernelGGL(nan_images_kernel, dim3((unsigned)(blocks < 128 ? blocks : 128), B), dim3(256), 0, (hipStream_t)stream, img,
+                     (long long)n, keep_count);
   return nbm_launch_status();
 }
 

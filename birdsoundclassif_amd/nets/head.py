@@ -21,18 +21,19 @@ class Faster_RCNN(nn.Module):
     def forward_second_stage(self, *args, **kwargs):
         return self.fast_rcnn(*args, **kwargs)
 
-    def forward_first_stage_device(self, fpn_nhwc, segments=None):
+    def forward_first_stage_device(self, fpn_nhwc, segments=None, images=None):
         """-> (rois [B,cap,4], roi_scores, n_roi device int32 [B], cls NHWC, reg NHWC, raw cls NHWC); no host sync.  Every
-        segment of `segments` (int32 [2, B] device table; None: the whole batch) is one model call of its own."""
+        segment of `segments` (int32 [2, B] device table; None: the whole batch) is one model call of its own.  `images`: the
+        input batch; an image that holds a NaN fails its model call (`ProposalLayer.forward_device`)."""
         cls, reg, cls_raw = self.rpn.forward_nhwc(fpn_nhwc)
         with torch.no_grad():
-            rois, scores, n_roi = self.prop_layer.forward_device(cls.detach(), reg.detach(), segments=segments)
+            rois, scores, n_roi = self.prop_layer.forward_device(cls.detach(), reg.detach(), segments=segments, images=images)
         return rois, scores, n_roi, cls, reg, cls_raw
 
-    def forward_first_stage(self, fpn_pyramid_out, host_work=None):
+    def forward_first_stage(self, fpn_pyramid_out, host_work=None, images=None):
         """fpn_pyramid_out: list of NCHW-shaped maps -> (rois [B,R,4] | empty, cls_scores, bbox_reg) (head.py:32-38)."""
         fm = [f.permute(0, 2, 3, 1).contiguous() for f in fpn_pyramid_out]
-        rois, _, n_roi, cls, reg, _ = self.forward_first_stage_device(fm)
+        rois, _, n_roi, cls, reg, _ = self.forward_first_stage_device(fm, images=images)
         # the RoI count goes to pinned memory NOW, with an event behind it: the host will wait for THAT, not for what `host_work`
         # queues after it (first-stage loss, early backward pass of the RPN branch: `n_roi.item()` waited for all of it -- 5 ms
         # during which the host could already build the proposal targets)

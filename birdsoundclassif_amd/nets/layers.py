@@ -175,8 +175,10 @@ class ProposalLayer(nn.Module):
             self._anchors[key] = torch.from_numpy((a + s).reshape(-1, 4).astype(np.float32)).to(device)
         return self._anchors[key]
 
-    def forward_device(self, cls_nhwc, reg_nhwc, segments=None):
+    def forward_device(self, cls_nhwc, reg_nhwc, segments=None, images=None):
         """-> (rois [B,post_n,4], scores [B,post_n], n_roi int32 [B] on device); n_roi[b] = 0 <=> "RPN failed".
+        `images` (the batch the maps were computed from, [B, ...]): an image that holds a NaN keeps no anchor, like the
+        reference's, whose NaN reaches every RPN output (the clamps of the convolution epilogues here drop it).
         The minima of layers.py:287 / nets_utils.py:236 (and the "RPN failed" rule) are taken per segment of `segments`
         (int32 [2, B] device table, `ops.segment_table` / `ops.batch_segments`), each segment one model call of the
         reference; None: the whole batch is one call."""
@@ -188,6 +190,8 @@ class ProposalLayer(nn.Module):
         anchors = self.anchors(h, w, cls_nhwc.device)
         boxes, keys, cnt = ops.rpn_decode(cls_nhwc, reg_nhwc, anchors, n_anchor, cfg.img_width, cfg.img_height,
                                           cfg.min_threshold)
+        if images is not None:
+            ops.nan_images_fail(images, cnt)
         cap = _pow2_cap(pre)
         sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, cfg.rcnn_batch_size, cap, segments=segments)
         return ops.nms_batched(sb, ss, n_sel, cfg.nms_thresh, post, segments=segments)

@@ -89,7 +89,8 @@ class NbmModel(nn.Module):
         gradient to come (evaluation) not even the RPN pattern is formed: the RPN's first block is composed with the map's own
         convolution; `ondemand.pattern_materialize(map)` forms the pattern pixels for a caller that wants to read them."""
         fpn_out = self._fpn_nhwc(samples, lazy=lazy)
-        rois, cls, reg = self.head.forward_first_stage([f.permute(0, 3, 1, 2) for f in fpn_out], host_work)
+        rois, cls, reg = self.head.forward_first_stage([f.permute(0, 3, 1, 2) for f in fpn_out], host_work,
+                                                          images=samples.detach().contiguous())
         return {'rois': rois, 'rpn_cls_scores': cls, 'rpn_bbox_reg': reg,
                 'fpn_out': [f.permute(0, 3, 1, 2) for f in fpn_out]}
 
@@ -134,7 +135,7 @@ class NbmModel(nn.Module):
         NotImplementedError on a transformer head with B > 1: a test of the suite pins that refusal, and `detect` is this
         method behind that guard."""
         fpn_out = self._fpn_nhwc(samples, lazy=True)
-        rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, segments=segments)
+        rois, _, n_roi, _, _, _ = self.head.forward_first_stage_device(fpn_out, segments=segments, images=samples.contiguous())
         return self.head.fast_rcnn.detect_device(fpn_out, rois, n_roi, nms_thresh, min_score,
                                                  segments=segments if self.args.tf_rcnn else None)
 

@@ -737,6 +737,16 @@ def rpn_decode(cls, reg, anchors, n_anchor, img_w, img_h, min_size):
     return boxes, keys, cnt
 
 
+def nan_images_fail(images, keep_count):
+    """images [B, ...] (contiguous fp32), keep_count int32 [B] of `rpn_decode` (in place): an image that holds a NaN keeps no
+    anchor, as in the reference, where the NaN reaches every RPN output and no comparison with it is true."""
+    _chk(images, name='images')
+    B = images.shape[0]
+    _chk_counts(keep_count, B, 'keep_count')
+    check(lib().nbm_nan_images(_ptr(images), B, images.numel() // B, _ptr(keep_count), _stream()), 'nbm_nan_images')
+    return keep_count
+
+
 def proposal_iou(rois, gt, n_gt):
     """rois [B,R,4], gt [B,G,4] (padded), n_gt int32 [B] -> (mx [B,R+G] best IoU of every proposal / ground-truth box with the
     image's ground-truth boxes, asg int32 [B,R+G] index of the first best box): reference layers.py:320-330."""

@@ -421,6 +421,11 @@ int nbm_rpn_decode(const float* cls, const float* reg, const float* anchors /*[K
                    int n_anchor /*A: anchors per location*/, int img_w, int img_h, int min_size, float* boxes,
                    uint32_t* keys, int* keep_count, void* stream);
 
+/* Input images that hold a NaN keep no anchor: keep_count[b] = 0 for every image b of img [B][n] with a NaN among its n
+ * values (the reference's NaN reaches every RPN output, and no comparison with NaN is true).  Launch after nbm_rpn_decode
+ * on the same stream, before nbm_rpn_select. */
+int nbm_nan_images(const float* img, int B, int64_t n, int* keep_count, void* stream);
+
 /* Proposal counts.  Every count pointer of this section (n_sel, n_in, n_out, n_roi) is a device int32 [B], one count
  * per image.  How the images are coupled is decided by the segment table `seg` of the two entry points below, a device
  * int32 [2][B]: seg[b] = first image of b's segment, seg[B + b] = its image count.  Each contiguous segment is one model
