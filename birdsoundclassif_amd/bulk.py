@@ -23,11 +23,13 @@ had been run alone.
 
 Multi-GPU: one process per GPU, files sharded `files[rank::world]`, no data-path collective (`nbm_detect.py` does the sharding).
 """
+import itertools
 import os
 import queue
 import struct
 import threading
 import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -66,23 +68,28 @@ class GraphedDetector:
         """`fmt` = (format tag, bits, channels) of the clips' payload (`wav_header`): the static inputs `pcms` are then uint8
         [batch, row bytes rounded up to 16] batches of raw payload rows, and `ops.wav_decode` + the float front end (resampler
         for any rate but 44.1 kHz) are captured in front of the detector.  None = mono 16-bit PCM given as int16 samples."""
-        from . import ops
-        self.model, self.batch, self.sr, self.lanes = model.eval(), batch, sr, max(1, int(lanes))
-        self.fmt, self.n_samples = (tuple(int(v) for v in fmt) if fmt is not None else None), int(n_samples)
+        self.sr, self.n_samples, self.independent, lanes = sr, int(n_samples), independent, max(1, int(lanes))
+        self.fmt = tuple(int(v) for v in fmt) if fmt is not None else None
         if self.fmt is not None and not decodable(*self.fmt):
             raise NotImplementedError(f'wav format tag {fmt[0]} with {fmt[1]} bits per sample and {fmt[2]} channels')
-        self.fes = [SpectrogramFrontEnd(device) for _ in range(self.lanes)]
-        self.fe = self.fes[0]
-        self.min_score, self.nms_thresh, self.independent = min_score, nms_thresh, independent
         if not independent:
             check_head_segment(model, batch, 'clip batch (--bulk_batch)')
-        self.n44 = n_samples * (2 if sr * 2 == self.fe.FREQ else 1) if fmt is None else samples_44k(sr, n_samples)
-        self.n_img = self.fe.n_images(self.fe.n_frames(self.n44))
-        if self.n_img != 1:
+        self.n44, self.n_img = samples_44k(sr, n_samples), 1
+        if not single_window(self.n44):
             raise NotImplementedError('GraphedDetector handles clips that fit one 1024-column window (<= 3.06 s)')
         shape, dtype = ((batch, n_samples), torch.int16) if fmt is None else ((batch, payload_pitch(self.fmt, n_samples)), torch.uint8)
-        self.pcms = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(self.lanes)]   # static graph inputs
+        self.pcms = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(lanes)]   # static graph inputs
         self.pcm = self.pcms[0]
+        self._start(model, batch, lanes, device, min_score, nms_thresh)
+
+    def _start(self, model, batch, lanes, device, min_score, nms_thresh):
+        """What every detector is made of besides its static inputs (which exist by now: the warm-up reads them): a front end
+        per lane, the streams, the lanes' scratch, and the captured graph."""
+        from . import ops
+        self.model, self.batch, self.lanes = model.eval(), batch, lanes
+        self.min_score, self.nms_thresh = min_score, nms_thresh
+        self.fes = [SpectrogramFrontEnd(device) for _ in range(self.lanes)]
+        self.fe = self.fes[0]
         self.stream = torch.cuda.Stream()
         self.side = [torch.cuda.Stream() for _ in range(self.lanes - 1)]
         self.lane_ids = self._claim_lanes(self, self.lanes)
@@ -214,7 +221,7 @@ def decodable(tag, bits, channels):
 
 def is_pcm16_mono(fmt, sr):
     """The format with an exact-integer front end of its own (`nbm_pcm16_to_wave`): its payload IS the int16 sample row."""
-    return tuple(fmt) == (1, 16, 1) and sr in RECORDING_RATES
+    return tuple(fmt) == (1, 16, 1) and sr in (22050, 44100)
 
 
 def payload_pitch(fmt, n):
@@ -237,8 +244,9 @@ def rate_ok(sr):
     return sr >= 1 and resample_table_size(sr, SpectrogramFrontEnd.FREQ) <= MAX_RESAMPLE_TABLE
 
 
-# the front end's default geometry (SpectrogramFrontEnd(dt=0.003, w_pix=1024)), which both routes and the CLI run with
-HOP_LENGTH, W_PIX = int(SpectrogramFrontEnd.FREQ * 0.003), 1024
+# the front end's default geometry (SpectrogramFrontEnd(dt=0.003, overlap_spectro=0.2, w_pix=1024): STFT hop, columns of a window,
+# columns between windows), which both routes and the CLI run with; chunk and file limits are SpectrogramFrontEnd's own
+HOP_LENGTH, W_PIX, HOP_SPECTRO = int(SpectrogramFrontEnd.FREQ * 0.003), 1024, int(0.8 * 1024)
 
 
 def single_window(n44):
@@ -246,70 +254,112 @@ def single_window(n44):
     return 1 + n44 // HOP_LENGTH <= W_PIX
 
 
+def recording_windows(sr, n):
+    """Number of spectrogram windows of a file of n samples per channel at any rate `sr` (prepare_dataset.py:267, per-chunk
+    frame counts of the STFT above 5e7 samples of the 44.1 kHz signal like SpectrogramFrontEnd.spectrogram_db)."""
+    n44, chunk = samples_44k(sr, n), SpectrogramFrontEnd.MAX_CHUNK
+    if n44 < chunk:
+        L = 1 + n44 // HOP_LENGTH
+    else:
+        L = sum(1 + (min(n44, (k + 1) * chunk) - k * chunk) // HOP_LENGTH for k in range(int(n44 / chunk) + 1))
+    return max(1, int(1 + np.ceil((L - W_PIX) / HOP_SPECTRO)))
+
+
+class WavInfo(NamedTuple):
+    """What the chunk headers of a wav file say (`wav_header`), and every routing decision that follows from them."""
+    path: str
+    fmt: tuple             # (format tag, bits, channels)
+    sr: int
+    n: int                 # frames = samples per channel
+    offset: int            # byte offset of the samples
+
+    @classmethod
+    def probe(cls, path):
+        tag, nch, sr, bits, n, off = wav_header(path)
+        return cls(path, (tag, bits, nch), sr, n, off)
+
+    @property
+    def nbytes(self):
+        return self.n * self.fmt[2] * (self.fmt[1] // 8)
+
+    @property
+    def n44(self):
+        return samples_44k(self.sr, self.n)
+
+    @property
+    def decodable(self):
+        """A payload the device decoder and the resampler take: both bulk routes read nothing else."""
+        return decodable(*self.fmt) and rate_ok(self.sr) and self.n > 0
+
+    @property
+    def int16_route(self):
+        """Mono PCM16 at 22.05 / 44.1 kHz: the samples go to the exact-integer front end as they are, undecoded."""
+        return is_pcm16_mono(self.fmt, self.sr)
+
+    @property
+    def clip(self):
+        """A file of one spectrogram window: the clip route (`detect_files`) takes groups of equal `group_key`."""
+        return self.decodable and single_window(self.n44)
+
+    @property
+    def recording(self):
+        """A file of any number of windows (a clip too) up to the 1.5e8-sample limit past which the reference splits the file
+        (process_long_file): the recording route (`detect_recordings`) takes it."""
+        return self.decodable and self.n44 <= SpectrogramFrontEnd.MAX_ONE_PASS
+
+    @property
+    def windows(self):
+        return recording_windows(self.sr, self.n)
+
+    @property
+    def group_key(self):
+        return (*self.fmt, self.sr, self.n)
+
+
+def probe_files(files):
+    """{file: its WavInfo, or None for a header that cannot be read}; every file is opened once.  Whatever is None, neither
+    `clip` nor `recording`, stays with the per-file driver: compressed formats, more than 8 channels, longer files."""
+    infos = {}
+    for f in files:
+        try:
+            infos[f] = WavInfo.probe(f)
+        except (OSError, ValueError, struct.error):
+            infos[f] = None
+    return infos
+
+
+def clip_groups(infos):
+    """[(group_key, [WavInfo by path])] of the `clip` files among the WavInfos, in the order the CLI takes the groups: mono PCM16
+    at 22.05 / 44.1 kHz (`int16_route`) first, then the other formats, each by ascending key."""
+    clips = sorted((i for i in infos if i.clip), key=lambda i: (not i.int16_route, i.group_key, i.path))
+    return [(key, list(group)) for key, group in itertools.groupby(clips, key=lambda i: i.group_key)]
+
+
 def read_payload(path, out=None):
     """The sample bytes of a wav file, undecoded: -> ((tag, bits, channels), sample rate, frames, uint8 buffer [frames * frame
-    bytes]).  The chunk headers are parsed (`wav_header`) and the payload is read straight into `out` (a writable uint8 numpy
-    array, e.g. a row of a pinned batch; it must be large enough) or, by default, into a fresh pinned tensor, whose numpy
-    view is returned -- no decode, no per-sample work.  A truncated payload gives its whole frames, like `read_wav`."""
-    tag, nch, sr, bits, n, off = wav_header(path)
-    if not decodable(tag, bits, nch):
+    bytes]).  The chunk headers are parsed (`wav_header`; a WavInfo in place of the path spares that) and the payload is read
+    straight into `out` (a writable uint8 numpy array, e.g. a row of a pinned batch; it must be large enough) or, by default,
+    into a fresh pinned tensor, whose numpy view is returned -- no decode, no per-sample work.  A truncated payload gives its
+    whole frames, like `read_wav`."""
+    info = path if isinstance(path, WavInfo) else WavInfo.probe(path)
+    path, nbytes = info.path, info.nbytes
+    if not decodable(*info.fmt):
+        tag, bits, nch = info.fmt
         raise NotImplementedError(f'{path}: wav format tag {tag} with {bits} bits per sample and {nch} channels')
-    nbytes = n * nch * (bits // 8)
     if out is None:
         pin = torch.empty((max(1, nbytes),), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
         out = pin.numpy()
     if out.dtype != np.uint8 or out.ndim != 1 or len(out) < nbytes:
         raise ValueError(f'{path}: a payload of {nbytes} bytes does not fit the buffer')
     with open(path, 'rb', buffering=0) as f:
-        f.seek(off)
+        f.seek(info.offset)
         got, view = 0, memoryview(out)[:nbytes]
         while got < nbytes:
             k = f.readinto(view[got:])
             if not k:
                 raise ValueError(f'{path}: the file shrank while it was read')
             got += k
-    return (tag, bits, nch), sr, n, out[:nbytes]
-
-
-def format_groups(files):
-    """`bulk_groups` for every format the device decoder takes: {(tag, bits, channels, sample rate, frames): [files]} of the
-    clips whose 44.1 kHz signal fills exactly one spectrogram window, and the rest.  Applied to what `bulk_groups` leaves
-    over it yields the clip groups of the other formats (mono PCM16 at 22.05 / 44.1 kHz keeps its own route)."""
-    groups, rest = {}, []
-    for f in files:
-        try:
-            tag, nch, sr, bits, n, _ = wav_header(f)
-        except (OSError, ValueError, struct.error):
-            rest.append(f)
-            continue
-        ok = decodable(tag, bits, nch) and n > 0 and rate_ok(sr)
-        ok = ok and single_window(samples_44k(sr, n))
-        if ok:
-            groups.setdefault((tag, bits, nch, sr, n), []).append(f)
-        else:
-            rest.append(f)
-    return groups, rest
-
-
-def bulk_groups(files):
-    """Splits a file list into {(sample rate, n_samples): [files]} of the clips the graphed path takes -- mono 16-bit PCM at
-    22.05 or 44.1 kHz that fill exactly one spectrogram window -- and the rest (any other format, length or an unreadable
-    header), which goes through the per-file driver."""
-    groups, rest = {}, []
-    for f in files:
-        try:
-            tag, nch, sr, bits, n, _ = wav_header(f)
-        except (OSError, ValueError, struct.error):
-            rest.append(f)
-            continue
-        ok = tag == 1 and nch == 1 and bits == 16 and sr in (22050, 44100) and n > 0
-        # one window <=> 1 + n44 // HOP_LENGTH <= W_PIX frames (prepare_dataset.py:126,267 with the default dt / w_pix)
-        ok = ok and 1 + (n * (2 if sr == 22050 else 1)) // int(44100 * 0.003) <= 1024
-        if ok:
-            groups.setdefault((sr, n), []).append(f)
-        else:
-            rest.append(f)
-    return groups, rest
+    return info.fmt, info.sr, info.n, out[:nbytes]
 
 
 def rows_to_result(rows, n, w_pix, hop, spectrogram_length, names=None):
@@ -350,10 +400,15 @@ def txt_path(wav_path):
     return wav_path.replace('.wav', '.txt')          # like the reference CLI (nbm_detect.py:27)
 
 
+def write_result(wav_path, res):
+    with open(txt_path(wav_path), 'w') as fh:
+        fh.write(str(res))
+
+
 def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_txt=True, depth=5, keep_results=True,
                  independent=True, stats=None, detector=None, lanes=None):
-    """Detects over equal-length wav files of one format and rate (single-window clips, see `bulk_groups` for mono 16-bit PCM
-    at 22.05 / 44.1 kHz and `format_groups` for everything else the device decoder takes): -> list of per-file output
+    """Detects over equal-length wav files of one format and rate (single-window clips of one `WavInfo.group_key`: mono
+    16-bit PCM at 22.05 / 44.1 kHz as int16 samples, everything else the device decoder takes as payload bytes): -> list of per-file output
     dicts in `files` order (None entries with keep_results=False); `<wav>.txt = str(dict)` written when `write_txt`.
     The last, partial batch is padded with silence and its padding results are dropped.  `stats` (dict) receives the stage
     times.  `detector`: a GraphedDetector to reuse (same batch / clip length / rate / lanes).
@@ -361,8 +416,9 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
     in groups of that many, in flight on the GPU together (see GraphedDetector)."""
     if not files:
         return []
-    tag, nch, sr, bits, n, _ = wav_header(files[0])
-    fmt = None if is_pcm16_mono((tag, bits, nch), sr) else (tag, bits, nch)     # None: the int16 samples themselves
+    first = WavInfo.probe(files[0])
+    sr, n = first.sr, first.n
+    fmt = None if first.int16_route else first.fmt                              # None: the int16 samples themselves
     n_batches = -(-len(files) // batch)
     if lanes is None:
         lanes = detector.lanes if detector is not None else int(os.environ.get('NBM_BULK_LANES', '2' if n_batches >= 4 else '1'))
@@ -433,8 +489,7 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
                     if keep_results:
                         out[i * batch + j] = res
                     if write_txt:
-                        with open(txt_path(f), 'w') as fh:
-                            fh.write(str(res))
+                        write_result(f, res)
                 t_write[0] += time.perf_counter() - t0
                 free_q.put(s)
         except BaseException as exc:                 # noqa: BLE001
@@ -501,58 +556,6 @@ def detect_files(model, files, batch=64, min_score=0.2, bird_dict=None, write_tx
 # proposal counts (and the transformer head's attention) coupled within the segment only (`NbmModel.detect_calls`), so every window comes out as the
 # per-file driver's call computes it, while windows of several files fill one launch.
 
-RECORDING_RATES = (22050, 44100)
-
-
-def recording_windows(sr, n, w_pix=1024, hop_img=819, hop=int(44100 * 0.003), max_chunk=int(5e7)):
-    """Number of spectrogram windows of a file of n samples per channel at any rate `sr` (prepare_dataset.py:267, per-chunk
-    frame counts of the STFT above 5e7 samples of the 44.1 kHz signal like SpectrogramFrontEnd.spectrogram_db)."""
-    n44 = samples_44k(sr, n)
-    if n44 < max_chunk:
-        L = 1 + n44 // hop
-    else:
-        L = sum(1 + (min(n44, (k + 1) * max_chunk) - k * max_chunk) // hop for k in range(int(n44 / max_chunk) + 1))
-    return max(1, int(1 + np.ceil((L - w_pix) / hop_img)))
-
-
-def recording_files(files):
-    """Splits a file list into the files the recording route takes -- mono 16-bit PCM at 22.05 or 44.1 kHz, not longer than
-    the 1.5e8-sample limit past which the reference splits the file (process_long_file) -- as [(file, windows)], and the rest
-    (other formats, unreadable headers, longer files), which stays with the per-file driver."""
-    take, rest = [], []
-    max_l = int(15e7) - int(15e7) % 44100
-    for f in files:
-        try:
-            tag, nch, sr, bits, n, _ = wav_header(f)
-        except (OSError, ValueError, struct.error):
-            rest.append(f)
-            continue
-        n44 = n * (2 if sr == 22050 else 1)
-        if tag == 1 and nch == 1 and bits == 16 and sr in RECORDING_RATES and 0 < n44 <= max_l:
-            take.append((f, recording_windows(sr, n)))
-        else:
-            rest.append(f)
-    return take, rest
-
-
-def decodable_recordings(files):
-    """`recording_files` for every format the device decoder takes, at any sample rate: [(file, windows)] of the files whose
-    44.1 kHz signal is not longer than the same limit, and the rest (compressed formats, more than 8 channels, unreadable
-    headers, longer files).  Applied to what `recording_files` leaves over it yields the recordings of the other formats."""
-    take, rest = [], []
-    max_l = int(15e7) - int(15e7) % 44100
-    for f in files:
-        try:
-            tag, nch, sr, bits, n, _ = wav_header(f)
-        except (OSError, ValueError, struct.error):
-            rest.append(f)
-            continue
-        if decodable(tag, bits, nch) and rate_ok(sr) and n > 0 and samples_44k(sr, n) <= max_l:
-            take.append((f, recording_windows(sr, n)))
-        else:
-            rest.append(f)
-    return take, rest
-
 
 class SegmentPacker:
     """Packs the segments of successive files into replays of `batch` window slots.  A segment (one model call of the per-file
@@ -602,20 +605,9 @@ before every replay: a tensor of its own, never one of the shared `ops.batch_seg
 
     def __init__(self, model, batch, min_score=0.2, nms_thresh=0.3, device='cuda'):
         from . import ops
-        self.model, self.batch, self.lanes = model.eval(), int(batch), 1
-        self.fe = SpectrogramFrontEnd(device)
-        self.fes = [self.fe]
-        self.min_score, self.nms_thresh = min_score, nms_thresh
-        self.table = torch.zeros((self.batch, ops.WINDOW_ENTRY_WORDS), dtype=torch.int64, device=device)
-        self.seg = ops.segment_table([1] * self.batch, device)
-        self.stream = torch.cuda.Stream()
-        self.side = []
-        self.lane_ids = self._claim_lanes(self, 1)
-        try:
-            self._capture(ops)
-        except BaseException:
-            self.close()
-            raise
+        self.table = torch.zeros((int(batch), ops.WINDOW_ENTRY_WORDS), dtype=torch.int64, device=device)
+        self.seg = ops.segment_table([1] * int(batch), device)
+        self._start(model, int(batch), 1, device, min_score, nms_thresh)
 
     def _run(self, k=0):
         from . import ops
@@ -637,7 +629,7 @@ RECORDING_AHEAD_BYTES = 4 << 30
 def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=None, write_txt=True, keep_results=True,
                       stats=None, detector=None, depth=4, ahead_bytes=RECORDING_AHEAD_BYTES):
     """Detects over recordings of any number of windows, in any format the device decoder takes and at any sample rate
-    (`recording_files`, `decodable_recordings`), through one captured graph:
+    (`WavInfo.recording`), through one captured graph:
     -> list of per-file output dicts in `files` order, each exactly `run_detection(model, cfg, f, ..., bs=bs)`'s (None for
     keep_results=False and for rejected files); `<wav>.txt = str(dict)` written when `write_txt`.
 
@@ -685,11 +677,11 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
                     break
                 t0 = time.perf_counter()
                 try:
-                    tag, nch, sr, bits, n, _ = wav_header(f)
-                    if not decodable(tag, bits, nch) or not rate_ok(sr) or n == 0:
-                        raise ValueError(f'{f}: format tag {tag}, {bits} bits, {nch} channels, {sr} Hz, {n} frames is not a '
-                                         'recording the route takes')
-                    nbytes = n * nch * (bits // 8)
+                    info = WavInfo.probe(f)
+                    if not info.decodable:
+                        raise ValueError(f'{f}: format tag {info.fmt[0]}, {info.fmt[1]} bits, {info.fmt[2]} channels, {info.sr} Hz, '
+                                         f'{info.n} frames is not a recording the route takes')
+                    nbytes = info.nbytes
                     t_read[0] += time.perf_counter() - t0
                     with room:                     # one file may always be held, whatever its size
                         while held[0] and held[0] + nbytes > ahead_bytes and not stop.is_set():
@@ -701,9 +693,7 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
                             pin = torch.empty((1, nbytes), dtype=torch.uint8, pin_memory=True)
                         except RuntimeError as exc:           # no pinned memory of that size: the per-file driver reads the file
                             raise OSError(f'{f}: {exc}') from None
-                        fmt, sr, n, _ = read_payload(f, pin.numpy()[0])
-                        if n * fmt[2] * (fmt[1] // 8) != nbytes:
-                            raise ValueError(f'{f}: the file changed while it was read')
+                        fmt, sr, n, _ = read_payload(info, pin.numpy()[0])
                     except BaseException:
                         with room:
                             held[0] -= nbytes
@@ -732,8 +722,7 @@ def detect_recordings(model, files, batch=64, bs=4, min_score=0.2, bird_dict=Non
                 if keep_results:
                     out[i] = res
                 if write_txt:
-                    with open(txt_path(files[i]), 'w') as fh:
-                        fh.write(str(res))
+                    write_result(files[i], res)
                 t_write[0] += time.perf_counter() - t0
         except BaseException as exc:                 # noqa: BLE001
             err.append(exc)

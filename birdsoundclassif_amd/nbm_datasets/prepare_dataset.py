@@ -114,6 +114,7 @@ class SpectrogramFrontEnd:
 
     MAX_CHUNK = int(5e7)           # STFT chunk length in 44.1 kHz samples (reference prepare_dataset.py:234)
     MAX_FILE = int(15e7)           # beyond this the reference goes through process_long_file (:187-225)
+    MAX_ONE_PASS = MAX_FILE - MAX_FILE % FREQ      # its max_l: the longest 44.1 kHz signal transformed in one piece (:189)
 
     def _source(self, dtype, n, sr):
         """How the 44.1 kHz signal is obtained from the input rows `x` (int16 PCM or float32 samples in [-1, 1)):
@@ -163,7 +164,7 @@ class SpectrogramFrontEnd:
         if src[0] == 'f32' and x.dtype == torch.int16:
             x = x.to(torch.float32) * (1.0 / 32768.0)             # exact
         n44 = src[1]
-        if n44 > self.MAX_FILE - self.MAX_FILE % self.FREQ:
+        if n44 > self.MAX_ONE_PASS:
             raise ValueError('rows longer than 1.5e8 samples are split by File_Processor.process_long_file first '
                              '(prepare_dataset.py:187-225)')
         if n44 < self.MAX_CHUNK:

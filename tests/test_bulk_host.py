@@ -31,10 +31,23 @@ def test_wav_header_and_groups(tmp_path):
     assert bulk.wav_header(p('a.wav')) == (1, 1, 22050, 16, 66150, 44)
     assert bulk.wav_header(p('stereo.wav'))[:5] == (1, 2, 22050, 16, 1000) and bulk.wav_header(p('stereo.wav'))[5] == 56
     files = sorted(str(f) for f in tmp_path.glob('*.wav'))
-    groups, rest = bulk.bulk_groups(files)
-    names = {k: sorted(os.path.basename(f) for f in v) for k, v in groups.items()}
-    assert names == {(22050, 66150): ['a.wav', 'b.wav'], (44100, 132300): ['c.wav'], (22050, (1023 * 132 + 131) // 2): ['edge_in.wav']}
-    assert sorted(os.path.basename(f) for f in rest) == ['edge_out.wav', 'junk.wav', 'long.wav', 'odd.wav', 'stereo.wav']
+    infos = {os.path.basename(f): i for f, i in bulk.probe_files(files).items()}
+    assert list(infos) == [os.path.basename(f) for f in files] and infos['junk.wav'] is None
+    assert infos['a.wav'] == (p('a.wav'), (1, 16, 1), 22050, 66150, 44) and infos['a.wav'].nbytes == 132300
+    names = {}
+    for name, i in infos.items():
+        if i and i.int16_route and i.clip:
+            names.setdefault(i.group_key, []).append(name)
+    assert names == {(1, 16, 1, 22050, 66150): ['a.wav', 'b.wav'], (1, 16, 1, 44100, 132300): ['c.wav'],
+                     (1, 16, 1, 22050, (1023 * 132 + 131) // 2): ['edge_in.wav']}
+    # what the int16 route's clip groups leave: longer files are recordings, other rates / channel counts clips of their own keys
+    assert sorted(n for n, i in infos.items() if not (i and i.int16_route and i.clip)) == \
+        ['edge_out.wav', 'junk.wav', 'long.wav', 'odd.wav', 'stereo.wav']
+    for name in ('edge_out.wav', 'long.wav'):
+        assert infos[name].int16_route and infos[name].recording and not infos[name].clip and infos[name].windows > 1
+    assert {infos[n].group_key for n in ('odd.wav', 'stereo.wav') if infos[n].clip and not infos[n].int16_route} == \
+        {(1, 16, 1, 16000, 48000), (1, 16, 2, 22050, 1000)}
+    assert all(i.recording and i.windows == 1 for i in infos.values() if i and i.clip)        # a clip is a recording of one window
 
 
 def _rows(seed, n, spectrogram_length):

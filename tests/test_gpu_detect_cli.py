@@ -114,7 +114,8 @@ def test_cli_bulk_route_writes_the_same_files_as_the_per_file_driver(tmp_path):
     synth.write_wav(str(a / 'long.wav'), long, 22050)                                               # two windows: per-file route
     synth.write_wav(str(a / 'short.wav'), synth.clip_pcm16(432)[:40000], 22050)                     # other length: alone in its group
     shutil.copytree(str(a), str(b))
-    groups, rest = bulk.bulk_groups(sorted(str(p) for p in a.glob('*.wav')))
+    infos = list(bulk.probe_files(sorted(str(p) for p in a.glob('*.wav'))).values())
+    groups, rest = dict(bulk.clip_groups(infos)), [i.path for i in infos if not (i.clip and i.int16_route)]
     assert sorted(len(v) for v in groups.values()) == [1, 12] and [os.path.basename(f) for f in rest] == ['long.wav']
     common = ['--ckpt', str(ck), '--min_score', '0.05', '--batch', '4', '--bird_dict', str(tmp_path / 'bird_dict.json')]
     nbm_detect.main(common + ['--audio_dir', str(a), '--bulk_batch', '8'])

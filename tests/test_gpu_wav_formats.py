@@ -216,7 +216,8 @@ def test_clip_route_takes_other_formats(tmp_path, models, sr, tag, bits, channel
         p = str(tmp_path / f'c{i}.wav')
         wavfmt.write(p, wavfmt.channels_of(synth.clip_pcm16(300 + i, n, sr), channels), sr, tag, bits)
         files.append(p)
-    groups, rest = bulk.format_groups(files)
+    infos = list(bulk.probe_files(files).values())
+    groups, rest = dict(bulk.clip_groups(infos)), [i.path for i in infos if not i.clip]
     assert list(groups) == [(tag, bits, channels, sr, n)] and rest == []
     got = bulk.detect_files(model, files, batch=4, min_score=0.05, bird_dict=names, write_txt=False)
     total = 0

@@ -74,7 +74,7 @@ def test_recording_windows_matches_the_front_end_window_count(sr, n):
     assert bulk.recording_windows(sr, n) == window_columns(Ls, 1024, 819)[0]
 
 
-def test_recording_files_takes_mono_pcm16_recordings_only(tmp_path):
+def test_int16_route_recordings_and_their_window_counts(tmp_path):
     d = str(tmp_path)
     synth.write_wav(os.path.join(d, 'clip.wav'), synth.clip_pcm16(1), 22050)
     synth.write_wav(os.path.join(d, 'rec.wav'), np.zeros(22050 * 40, np.int16), 22050)
@@ -86,9 +86,15 @@ def test_recording_files_takes_mono_pcm16_recordings_only(tmp_path):
         f.writeframes(np.zeros(2 * 22050 * 5, '<i2').tobytes())
     open(os.path.join(d, 'junk.wav'), 'wb').write(b'not a wav')
     files = sorted(os.path.join(d, f) for f in os.listdir(d))
-    take, rest = bulk.recording_files(files)
-    assert [(os.path.basename(f), w) for f, w in take] == [('clip.wav', 1), ('rec.wav', 17), ('rec44.wav', 3)]
-    assert sorted(os.path.basename(f) for f in rest) == ['junk.wav', 'odd_rate.wav', 'stereo.wav']
+    infos = bulk.probe_files(files)
+    assert list(infos) == files
+    take = [(os.path.basename(f), i.windows) for f, i in infos.items() if i and i.int16_route and i.recording]
+    assert take == [('clip.wav', 1), ('rec.wav', 17), ('rec44.wav', 3)]
+    rest = {os.path.basename(f): i for f, i in infos.items() if not (i and i.int16_route and i.recording)}
+    assert sorted(rest) == ['junk.wav', 'odd_rate.wav', 'stereo.wav'] and rest['junk.wav'] is None
+    # the other two are recordings of the decoder's formats
+    assert [(n, rest[n].recording, rest[n].windows) for n in ('odd_rate.wav', 'stereo.wav')] == \
+        [('odd_rate.wav', True, bulk.recording_windows(16000, 160000)), ('stereo.wav', True, bulk.recording_windows(22050, 110250))]
 
 
 def test_proposal_entry_points_take_a_segment_table():

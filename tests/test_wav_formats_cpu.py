@@ -1,5 +1,5 @@
-"""CPU: host side of the device wav decoder on the bulk routes -- the wider file classification beside `bulk_groups` /
-`recording_files`, the window count at any sample rate, and the raw payload reader against `read_wav`."""
+"""CPU: host side of the device wav decoder on the bulk routes -- the file classification (`probe_files`) over every format beside
+the int16 route's, the window count at any sample rate, and the raw payload reader against `read_wav`."""
 import os
 
 import numpy as np
@@ -54,23 +54,51 @@ def test_classification_beside_the_pcm16_functions(tmp_path):
     os.truncate(p('overlong.wav'), 44 + 3 * n_long)                            # sparse: the header must agree with the size
     files = sorted(str(f) for f in tmp_path.glob('*.wav'))
 
-    groups0, rest0 = bulk.bulk_groups(files)                                   # unchanged answers
-    assert {k: _names(v) for k, v in groups0.items()} == {(22050, 66150): ['clip_pcm16.wav']}
-    take0, others0 = bulk.recording_files(rest0)
-    assert [(os.path.basename(f), w) for f, w in take0] == [('rec_pcm16.wav', bulk.recording_windows(22050, 220500))]
+    infos = {os.path.basename(f): i for f, i in bulk.probe_files(files).items()}
+    assert list(infos) == _names(files) and infos['junk.wav'] is None
+    taken = {n: i for n, i in infos.items() if i and i.recording}
+    int16 = {n: i for n, i in taken.items() if i.int16_route}                  # the exact-integer front end's own format
+    assert {i.group_key: [n] for n, i in int16.items() if i.clip} == {(1, 16, 1, 22050, 66150): ['clip_pcm16.wav']}
+    assert [(n, i.windows) for n, i in int16.items() if not i.clip] == [('rec_pcm16.wav', bulk.recording_windows(22050, 220500))]
 
-    groups, rest = bulk.format_groups(rest0)
-    assert {k: _names(v) for k, v in groups.items()} == {v: [k] for k, v in clips.items()}
-    assert _names(rest) == sorted(list(recs) + ['rec_pcm16.wav', 'junk.wav', 'alaw.wav', 'nine.wav', 'overlong.wav'])
-    take, others = bulk.decodable_recordings(others0)
-    assert {os.path.basename(f): w for f, w in take} == {**recs, **{k: 1 for k in clips}}
-    assert _names(others) == ['alaw.wav', 'junk.wav', 'nine.wav', 'overlong.wav']
-    # on the whole folder the wider functions are supersets of the PCM16 ones
-    assert {os.path.basename(f) for f, _ in bulk.decodable_recordings(files)[0]} >= {'rec_pcm16.wav', 'clip_pcm16.wav'}
-    assert (1, 16, 1, 22050, 66150) in bulk.format_groups(files)[0]
+    others = {n: i for n, i in taken.items() if not i.int16_route}
+    assert {i.group_key: [n] for n, i in others.items() if i.clip} == {v: [k] for k, v in clips.items()}
+    assert _names(n for n, i in infos.items() if not (i and i.clip)) == \
+        sorted(list(recs) + ['rec_pcm16.wav', 'junk.wav', 'alaw.wav', 'nine.wav', 'overlong.wav'])
+    assert {n: i.windows for n, i in others.items()} == {**recs, **{k: 1 for k in clips}}
+    nobody = _names(n for n in infos if n not in taken)
+    assert nobody == ['alaw.wav', 'junk.wav', 'nine.wav', 'overlong.wav']
+    assert not any(infos[n].clip or infos[n].recording or infos[n].int16_route for n in nobody if infos[n])
+    assert all(i.recording and i.windows == 1 for i in infos.values() if i and i.clip)     # a clip is a recording of one window
     # exactly at the limit the file is taken
+    assert bulk.samples_44k(44100, infos['overlong.wav'].n) == n_long == SpectrogramFrontEnd.MAX_ONE_PASS + 1
     os.truncate(p('overlong.wav'), 44 + 3 * (n_long - 1))
-    assert _names(f for f, _ in bulk.decodable_recordings([p('overlong.wav')])[0]) == ['overlong.wav']
+    assert bulk.probe_files([p('overlong.wav')])[p('overlong.wav')].recording
+
+
+def test_every_header_is_read_once_and_clip_groups_come_in_the_cli_order(tmp_path, monkeypatch):
+    p = lambda n: str(tmp_path / n)
+    x = np.arange(22050 * 10, dtype=np.int16)
+    wavfmt.write(p('a_pcm16.wav'), x[:66150], 22050, 1, 16)
+    wavfmt.write(p('b_pcm16_44k.wav'), x[:100000], 44100, 1, 16)
+    wavfmt.write(p('c_f32.wav'), x[:32000], 32000, 3, 32)
+    wavfmt.write(p('d_pcm8.wav'), x[:32000], 32000, 1, 8)
+    wavfmt.write(p('e_st24.wav'), wavfmt.channels_of(x[:44100], 2), 44100, 1, 24)
+    wavfmt.write(p('f_rec.wav'), x, 22050, 1, 16)
+    open(p('junk.wav'), 'wb').write(b'not a wav file at all')
+    files = sorted(str(f) for f in tmp_path.glob('*.wav'))
+    opened, real = [], bulk.wav_header
+    monkeypatch.setattr(bulk, 'wav_header', lambda path: opened.append(path) or real(path))
+    infos = bulk.probe_files(files)
+    assert opened == files                                                     # the routing below opens nothing again
+    groups = bulk.clip_groups([i for i in infos.values() if i])
+    # mono PCM16 at 22.05 / 44.1 kHz first, then the other formats, each by ascending (tag, bits, channels, rate, frames)
+    assert [(k, _names(i.path for i in g)) for k, g in groups] == [
+        ((1, 16, 1, 22050, 66150), ['a_pcm16.wav']), ((1, 16, 1, 44100, 100000), ['b_pcm16_44k.wav']),
+        ((1, 8, 1, 32000, 32000), ['d_pcm8.wav']), ((1, 24, 2, 44100, 44100), ['e_st24.wav']), ((3, 32, 1, 32000, 32000), ['c_f32.wav'])]
+    left = [i for i in infos.values() if i and not i.clip]
+    assert [(os.path.basename(i.path), i.recording, i.windows) for i in left] == [('f_rec.wav', True, bulk.recording_windows(22050, 220500))]
+    assert opened == files
 
 
 def _front_end_frames(fe, sr, n):
