@@ -11,6 +11,7 @@ whole mechanism off (dense maps).
 import ctypes as C
 import os
 import weakref
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -19,6 +20,18 @@ from . import ops
 from .ops import check, lib, _ptr, _chk, _stream, gemm_conv, conv_wgrad
 
 LAZY_FINEST = os.environ.get('NBM_LAZY_FINEST', '1') != '0'
+COMPOSITE = os.environ.get('NBM_RPN_COMPOSITE', '1') != '0'     # evaluation mode: the RPN's reader composed with this convolution (rpn_composite)
+TRAIN_COMPOSITE = os.environ.get('NBM_RPN_COMPOSITE_TRAIN', '1') != '0'   # training: the same composition in the cell domain (train_composite_*)
+# The deferred lateral's OWN gradients from the consumer's backward pass: its pattern share rides in the cell-domain GEMMs (the
+# folded weights [U | alpha U W] give d/dt in the transform domain, the weight-gradient GEMMs already hold d/d(alpha U W)), its RoI
+# share runs on compact [tiles x 4 pixels] operands -- instead of three dense passes over the 18.9 GB gradient of the merged map
+LAT_CELL_BWD = os.environ.get('NBM_LAT_CELL_BWD', '1') != '0'
+# ... and then the only reader left of d/d(merged map) is the bilinear backward of the top-down merge: the RoI share stays in its
+# compact form (nbm_tiles_upsample_bilinear_bwd_add) and the map holds the pattern patches only, which lets that reader skip the rows
+# and columns between the patches (nbm_upsample_bilinear_bwd(pattern_stride): 61 % of 18.9 GB at B = 128)
+UPBWD_SPLIT = os.environ.get('NBM_UPBWD_SPLIT', '1') != '0'
+ZERO_POOL = os.environ.get('NBM_ZERO_POOL', '1') != '0'         # persistent gradient maps of a demand-driven level (see zero_acquire)
+ZERO_POOL_CHECK = os.environ.get('NBM_ZERO_POOL_CHECK', '0') == '1'      # tests: verify the buffer after every recycle (synchronises)
 LAZY_POISON = False                 # tests: fill the map with NaN first, so that a read of an unwritten pixel shows
 _LAZY = {}                          # data_ptr of the sparse map -> LazyMap
 _PATTERNS = {}
@@ -62,6 +75,9 @@ def wino23_pattern(B, H, W, stride, device, dilate=0):
         ry, rx = need(H, TH), need(W, TW)
         # planes i (rows of A^T = [1 1 1 0; 0 1 -1 -1]) a tile row needs: first pixel row -> {0,1,2}, second -> {1,2,3}
         planes_of = {0: 0, 1: 0b0111, 2: 0b1110, 3: 0b1111}
+
+        def plane_mask(cy, cx):                   # the planes 4 i + j that the tiles of class (cy, cx) compute
+            return sum(1 << (4 * i + j) for i in range(4) for j in range(4) if (planes_of[cy] >> i) & 1 and (planes_of[cx] >> j) & 1)
         lists, infos, n, n_eff = [], [], 0, 0.0
         for cy in (3, 2, 1):
             for cx in (3, 2, 1):
@@ -70,16 +86,8 @@ def wino23_pattern(B, H, W, stride, device, dilate=0):
                 if ids.size == 0:
                     continue
                 allt = (np.arange(B, dtype=np.int64)[:, None] * (TH * TW) + ids[None, :]).ravel()
-                pm = 0
-                for i in range(4):
-                    for j in range(4):
-                        if (planes_of[cy] >> i) & 1 and (planes_of[cx] >> j) & 1:
-                            pm |= 1 << (4 * i + j)
-                sm = 0
-                for pp in range(2):
-                    for qq in range(2):
-                        if (cy >> pp) & 1 and (cx >> qq) & 1:
-                            sm |= 1 << (2 * pp + qq)
+                pm = plane_mask(cy, cx)
+                sm = sum(1 << (2 * pp + qq) for pp in range(2) for qq in range(2) if (cy >> pp) & 1 and (cx >> qq) & 1)
                 pad = (-allt.size) % 128
                 lists.append(np.concatenate([allt, np.full(pad, -1, dtype=np.int64)]))
                 infos.append(np.full((allt.size + pad) // 128, pm | (sm << 16), dtype=np.int64))
@@ -106,9 +114,7 @@ def wino23_pattern(B, H, W, stride, device, dilate=0):
         tpm = np.zeros(TH * TW, dtype=np.int64)
         for cy in (3, 2, 1):
             for cx in (3, 2, 1):
-                pmv = sum(1 << (4 * i + j) for i in range(4) for j in range(4)
-                          if (planes_of[cy] >> i) & 1 and (planes_of[cx] >> j) & 1)
-                tpm[((ry == cy)[:, None] & (rx == cx)[None, :]).ravel()] = pmv
+                tpm[((ry == cy)[:, None] & (rx == cx)[None, :]).ravel()] = plane_mask(cy, cx)
         hit.tile_pm = torch.from_numpy(tpm.astype(np.int32)).to(device)
         hit.tiles = torch.from_numpy(blocks[order].ravel().astype(np.int32)).to(device)
         hit.blk_info = torch.from_numpy(infos.astype(np.uint32).view(np.int32)).to(device)
@@ -132,6 +138,11 @@ def wino23_pattern(B, H, W, stride, device, dilate=0):
     return hit
 
 
+def _rows_scratch_floats(H, W, C_):
+    """Floats per image of the row-transform scratch (dense layout: 4 planes x tile rows x (2 tile columns + 2) x channels)."""
+    return 4 * (-(-H // 2)) * (2 * (-(-W // 2)) + 2) * C_
+
+
 def _wino23_tiles_run(x, U, bias, y_ptr, tiles, n_blocks, n_listed, label, blk_info=None, dense_rows=False, skip_pattern=0,
                       accumulate=False, compact=False):
     """Rows transform + fused kernel for the listed tiles of x [B,H,W,C] -> pixels of the map at device address y_ptr.
@@ -139,8 +150,7 @@ def _wino23_tiles_run(x, U, bias, y_ptr, tiles, n_blocks, n_listed, label, blk_i
     3x3 / stride-S pattern of x read as zeros; accumulate: the result is added to the map (every tile listed once)."""
     B, H, W, C_ = x.shape
     N = U.shape[1]
-    per_img = 4 * (-(-H // 2)) * (2 * (-(-W // 2)) + 2) * C_
-    R, _ = ops._wino_scratch(x.device, B * per_img, 0)
+    R, _ = ops._wino_scratch(x.device, B * _rows_scratch_floats(H, W, C_), 0)
     st = _stream()
     nb_ptr = _ptr(n_blocks) if n_blocks is not None else None
     if ops.FLOPS is not None:
@@ -174,25 +184,32 @@ def _wino23_tiles_run(x, U, bias, y_ptr, tiles, n_blocks, n_listed, label, blk_i
 def lazy_chunk(x):
     """Images per launch of the sparse path: the row-transform scratch keeps its dense layout (holes unwritten)."""
     _, H, W, C_ = x.shape
-    per_img = 4 * (-(-H // 2)) * (2 * (-(-W // 2)) + 2) * C_ * 4
-    return max(1, min(x.shape[0], ops.WINO_CHUNK_BYTES // per_img))
+    return max(1, min(x.shape[0], ops.WINO_CHUNK_BYTES // (_rows_scratch_floats(H, W, C_) * 4)))
+
+
+# One batch chunk of a recorded RoI pooling: the tile list under its windows, the list's block count on the way to the host (pinned
+# int32 + the event behind the copy) and, where `lazy_complete` made the dilated list (tiles within a pixel of the windows), that list
+# and its count -- None otherwise
+RoiChunk = NamedTuple('RoiChunk', [('tiles', torch.Tensor), ('host', torch.Tensor), ('event', object), ('tiles_d', object), ('host_d', object)])
+# One RoI pooling that read a demand-driven map and recorded its lists: its RoIs as `nbm_roi_tiles` takes them + a RoiChunk per batch chunk
+RoiPooling = NamedTuple('RoiPooling', [('rois', torch.Tensor), ('n_roi', torch.Tensor), ('n_levels', int), ('level', int), ('fh', object),
+                                       ('fw', object), ('chunks', list)])
 
 
 class LazyMap:
     """Book-keeping of one demand-driven map: operands and, per batch chunk, the tile lists that were computed (pattern
-    list; per RoI pooling on the map a RoI list + its block count on the way to the host) -- the weight gradient sums over
+    list in `chunks`; per recorded RoI pooling on the map a RoiPooling in `rois`) -- the weight gradient sums over
     them.  The map itself is NOT referenced (an autograd node owns this object and the map owns the node: a cycle would keep
     12 GB alive until the garbage collector runs); its consumers keep it alive and hand it back to `lazy_complete`.
     The operands stay here for as long as the map lives, so EVERY RoI pooling on the map -- not only the first -- finds the
     tiles under its windows computed (`done` counts them); the state goes when the map does (`_forget`)."""
-    __slots__ = ('x', 'U', 'bias', 'skip', 'stride', 'chunks', 'roi', 'keep', 'sparse', 'overlap', 'lateral', 'rois', 'done', 'vg', 'cell_gb', 'cell_gb_done', 'vx', 'raw', 'pending', 'comp', '__weakref__')
+    __slots__ = ('x', 'U', 'bias', 'skip', 'stride', 'chunks', 'keep', 'sparse', 'overlap', 'lateral', 'rois', 'done', 'vg', 'cell_gb', 'cell_gb_done', 'vx', 'raw', 'pending', 'comp', '__weakref__')
 
     def __init__(self, x, U, bias, stride):
         self.x, self.U, self.bias, self.stride = x, U, bias, stride
         self.skip, self.chunks, self.keep, self.sparse, self.lateral = None, [], False, True, None
         self.overlap = False         # dense-looking level (every tile holds a pattern pixel) whose backward pass still goes through the cells
-        self.roi = []           # per RoI pooling: per chunk (tile list, pinned block count, event)
-        self.rois = []          # per RoI pooling: (rois, n_roi, n_levels, level, fh, fw)
+        self.rois = []          # one RoiPooling per RoI pooling that recorded its tile lists (`keep`)
         self.done = 0
         self.vg = None          # backward pass: {chunk: Vg} of the cell transforms, shared by the data and the weight gradient
         self.cell_gb = None     # ... and the bias gradient of the pattern pixels, summed by the same kernel
@@ -208,9 +225,9 @@ class LazyMap:
 
     def __del__(self):          # the pinned counters go back to the pool
         try:
-            for per_chunk in self.roi:
-                for entry in per_chunk:         # (tiles, host, event, dilated tiles, its host counter or None)
-                    _PINNED_FREE.extend(h for h in (entry[1], entry[4] if len(entry) > 4 else None) if h is not None)
+            for pooling in self.rois:
+                for ch in pooling.chunks:
+                    _PINNED_FREE.extend(h for h in (ch.host, ch.host_d) if h is not None)
         except Exception:       # interpreter shutdown
             pass
 
@@ -263,6 +280,15 @@ def _forget(table, key, ident):
         del table[key]
 
 
+def _register(table, t, state):
+    """`state` under the address of tensor `t` in a weak-keyed table: valid while `t` (or a view of it) is alive, gone with it
+    (operands included); entries of earlier forwards whose tensor died unclaimed are dropped first."""
+    for k in [k for k, v in table.items() if v[1]() is None]:
+        del table[k]
+    table[t.data_ptr()] = (state, weakref.ref(t))
+    weakref.finalize(t, _forget, table, t.data_ptr(), id(state))
+
+
 def _lateral_pattern_pass(x, ls, stride):
     """The lateral + merge on the pattern patches (`TilePattern.px_rows`) into the sparse map x."""
     B, H, W, N = x.shape
@@ -293,54 +319,60 @@ def conv1x1_lazy(t, wk, bias, alpha, up, stride, defer=False):
     ls = LateralState(t, wk, bias, alpha, up, deferred=defer, stride=stride)
     if not defer:
         _lateral_pattern_pass(x, ls, stride)
-    for k in [k for k, v in _LAZY_LATERAL.items() if v[1]() is None]:
-        del _LAZY_LATERAL[k]
-    _LAZY_LATERAL[x.data_ptr()] = (ls, weakref.ref(x))
-    weakref.finalize(x, _forget, _LAZY_LATERAL, x.data_ptr(), id(ls))
+    _register(_LAZY_LATERAL, x, ls)
     return x
 
 
 def _cell_operand(st, b0, nb, H, W, C_, x, n_out=0, ci=None):
     """A operand of the cell-domain plane GEMMs of batch chunk [b0, b0 + nb): the transformed 5x5 input patches, [25][cells][K].
     From the map x itself (K = C), or -- deferred lateral -- from the lateral's operands: [transform(up(x1) + b) | transform(t)],
-    K = C + Cin.  -> (V, M: views of the shared scratch, M with room for [25][cells][n_out]; K; cells).  Deferred lateral with a
-    backward pass to come (`st.keep`, chunk index `ci`): V is an allocation of its own, kept in st.vx for the weight gradient (8.8 GB
-    at B = 128 for -4 ms: the interpolating transform is not run twice)."""
+    K = C + Cin.  -> (V, M: views of the shared scratch, M with room for [25][cells][n_out]; K; cells).  With a backward pass to come
+    (`st.keep`, chunk index `ci`; the map source only on a level whose weight gradient runs in the cell domain): V is an allocation of
+    its own, kept in st.vx for the weight gradient (deferred lateral: 8.8 GB at B = 128 for -4 ms, the interpolating transform is not
+    run twice)."""
     T = cell_count(nb, H, W, st.stride)
     stream = _stream()
-    lt = st.lateral
-    if lt is not None and lt.deferred:
+    lt = st.lateral if st.lateral is not None and st.lateral.deferred else None
+    if lt is not None:
         Cin = lt.t.shape[-1]
-        K = C_ + Cin
-        if st.vx is not None and ci in st.vx:            # the forward pass left it here
-            return st.vx.pop(ci), ops._wino_scratch(lt.t.device, 25 * T * n_out, 0)[0], K, T
-        if st.keep and ci is not None and n_out:         # forward pass, a backward pass will follow
-            if st.vx is None:
-                st.vx = {}
-            V = st.vx[ci] = torch.empty((25 * T * K,), device=lt.t.device, dtype=torch.float32)
-            M = ops._wino_scratch(lt.t.device, 25 * T * n_out, 0)[0]
-        else:
-            V, M = ops._wino_scratch(lt.t.device, 25 * T * K, 25 * T * n_out)
+        K, dev, keep = C_ + Cin, lt.t.device, st.keep
+    else:
+        # the cell-domain weight gradient will want the same operand (7.5 GB at B = 128 for level P2: -2.4 ms)
+        K, dev, keep = C_, x.device, st.keep and (st.sparse or st.overlap)
+    if st.vx is not None and ci in st.vx:                # the forward pass left it here
+        return st.vx.pop(ci), ops._wino_scratch(dev, 25 * T * n_out, 0)[0], K, T
+    if keep and ci is not None and n_out:                # forward pass, a backward pass will follow
+        if st.vx is None:
+            st.vx = {}
+        V = st.vx[ci] = torch.empty((25 * T * K,), device=dev, dtype=torch.float32)
+        M = ops._wino_scratch(dev, 25 * T * n_out, 0)[0]
+    else:
+        V, M = ops._wino_scratch(dev, 25 * T * K, 25 * T * n_out)
+    if lt is not None:
         check(lib().nbm_cell_input_up(_ptr(lt.up[b0:b0 + nb]), _ptr(lt.bias), nb, H, W, C_, lt.up.shape[1], lt.up.shape[2], st.stride,
                                       _ptr(V), K, 0, stream), 'nbm_cell_input_up')
         check(lib().nbm_cell_input(_ptr(lt.t[b0:b0 + nb]), nb, H, W, Cin, st.stride, _ptr(V), K, C_, stream), 'nbm_cell_input')
-        return V, M, K, T
-    if st.vx is not None and ci in st.vx:                # the forward pass left it here
-        return st.vx.pop(ci), ops._wino_scratch(x.device, 25 * T * n_out, 0)[0], C_, T
-    if st.keep and ci is not None and n_out and (st.sparse or st.overlap):
-        # forward pass, the cell-domain weight gradient will want the same operand (7.5 GB at B = 128 for level P2: -2.4 ms)
-        if st.vx is None:
-            st.vx = {}
-        V = st.vx[ci] = torch.empty((25 * T * C_,), device=x.device, dtype=torch.float32)
-        M = ops._wino_scratch(x.device, 25 * T * n_out, 0)[0]
     else:
-        V, M = ops._wino_scratch(x.device, 25 * T * C_, 25 * T * n_out)
-    check(lib().nbm_cell_input(_ptr(x[b0:b0 + nb]), nb, H, W, C_, st.stride, _ptr(V), C_, 0, stream), 'nbm_cell_input')
-    return V, M, C_, T
+        check(lib().nbm_cell_input(_ptr(x[b0:b0 + nb]), nb, H, W, C_, st.stride, _ptr(V), C_, 0, stream), 'nbm_cell_input')
+    return V, M, K, T
 
 
-COMPOSITE = os.environ.get('NBM_RPN_COMPOSITE', '1') != '0'     # evaluation mode: the RPN's reader composed with this convolution (rpn_composite)
-TRAIN_COMPOSITE = os.environ.get('NBM_RPN_COMPOSITE_TRAIN', '1') != '0'   # training: the same composition in the cell domain (train_composite_*)
+def _cell_pattern_pass(st, ci, b0, nb, x, Uc, y, label=None):
+    """The pattern pixels of batch chunk `ci` of the map y through the cell transforms: patch transform (`_cell_operand`), the 25 plane
+    GEMMs with Uc ([25][N][K]: Ucell, or Ufold behind a deferred lateral), block transform + bias into y.  `label`: profile label of
+    the GEMMs (None: the caller's)."""
+    _, H, W, C_ = x.shape
+    N = y.shape[-1]
+    Vx, M, K, T = _cell_operand(st, b0, nb, H, W, C_, x, n_out=N, ci=ci)
+    keep_label = ops._PROFILE_LABEL
+    if label is not None:
+        ops._PROFILE_LABEL = label
+    try:
+        gemm_conv(Vx, Uc, M, B=1, H=T, W=1, Cin=K, N=N, groups=25, x_gs=T * K, w_gs=N * K, y_gs=T * N)
+    finally:
+        ops._PROFILE_LABEL = keep_label
+    check(lib().nbm_cell_output(_ptr(M), _ptr(st.bias), nb, H, W, N, st.stride, C.c_void_p(y.data_ptr() + b0 * H * W * N * 4), _stream()),
+          'nbm_cell_output')
 
 
 def conv3x3_winograd_lazy(x, U, bias, stride, Ucell=None, fold=None, keep=False, raw=None):
@@ -392,26 +424,14 @@ def conv3x3_winograd_lazy(x, U, bias, stride, Ucell=None, fold=None, keep=False,
             st.skip = None
             continue
         if cell_ok:                                  # (3x3 blocks of different cells never overlap)
-            stream = _stream()
-            Vx, M, K, T = _cell_operand(st, b0, nb, H, W, C_, x, n_out=N, ci=ci)
-            keep_label, ops._PROFILE_LABEL = ops._PROFILE_LABEL, ('cell-fwd', H, W)
-            try:
-                gemm_conv(Vx, Ufold if Ufold is not None else Ucell, M, B=1, H=T, W=1, Cin=K, N=N, groups=25, x_gs=T * K, w_gs=N * K,
-                          y_gs=T * N)
-            finally:
-                ops._PROFILE_LABEL = keep_label
-            check(lib().nbm_cell_output(_ptr(M), _ptr(bias), nb, H, W, N, stride, C.c_void_p(y.data_ptr() + b0 * img_bytes), stream),
-                  'nbm_cell_output')
+            _cell_pattern_pass(st, ci, b0, nb, x, Ufold if Ufold is not None else Ucell, y, label=('cell-fwd', H, W))
             # the RoI phase skips nothing: every pixel the RoI pooling reads is then a value of the dense F(2x2,3x3) convolution, bit
             # for bit; only the RPN's strided reader sees the cell values (1 tile in 16 is all pattern pixels: +6 % RoI-phase tiles)
             st.skip = None
             continue
         _wino23_tiles_run(x[b0:b0 + nb], U, bias, y.data_ptr() + b0 * img_bytes, pat.tiles, None, pat.n_eff, 'wino23', pat.blk_info,
                           dense_rows=pat.frac == 1.0)
-    for k in [k for k, v in _LAZY.items() if v[1]() is None]:      # maps of earlier forwards that were never completed
-        del _LAZY[k]
-    _LAZY[y.data_ptr()] = (st, weakref.ref(y))      # valid while the map object itself (or a view of it) is alive
-    weakref.finalize(y, _forget, _LAZY, y.data_ptr(), id(st))     # ... and gone with it (operands included)
+    _register(_LAZY, y, st)
     return y, st
 
 
@@ -423,15 +443,16 @@ def pattern_materialize(fm):
         return
     Ucell, Ufold = st.pending
     st.pending = None
-    B, H, W, N = fm.shape
-    C_ = st.x.shape[-1]
-    img_bytes = H * W * N * 4
-    stream = _stream()
-    for ci, (b0, nb, pat) in enumerate(st.chunks):
-        Vx, M, K, T = _cell_operand(st, b0, nb, H, W, C_, st.x, n_out=N, ci=ci)
-        gemm_conv(Vx, Ufold if Ufold is not None else Ucell, M, B=1, H=T, W=1, Cin=K, N=N, groups=25, x_gs=T * K, w_gs=N * K, y_gs=T * N)
-        check(lib().nbm_cell_output(_ptr(M), _ptr(st.bias), nb, H, W, N, st.stride, C.c_void_p(fm.data_ptr() + b0 * img_bytes), stream),
-              'nbm_cell_output')
+    for ci, (b0, nb, _) in enumerate(st.chunks):
+        _cell_pattern_pass(st, ci, b0, nb, st.x, Ufold if Ufold is not None else Ucell, fm)
+
+
+def _tap_masks(H, W, S):
+    """-> (rm [OH], sm [OW]): per row / column of the cell grid of a 3x3 / stride S / pad 1 reader, which taps lie inside the map."""
+    OH, OW = (H - 1) // S + 1, (W - 1) // S + 1
+    rm = [sum(1 << r for r in range(3) if 0 <= S * oy - 1 + r < H) for oy in range(OH)]
+    sm = [sum(1 << c for c in range(3) if 0 <= S * ox - 1 + c < W) for ox in range(OW)]
+    return rm, sm
 
 
 _BORDER_IDX = {}
@@ -445,9 +466,8 @@ def _border_classes(nb, H, W, S, device):
     key = (nb, H, W, S, str(device))
     hit = _BORDER_IDX.get(key)
     if hit is None:
-        OH, OW = (H - 1) // S + 1, (W - 1) // S + 1
-        rm = [sum(1 << r for r in range(3) if 0 <= S * oy - 1 + r < H) for oy in range(OH)]
-        sm = [sum(1 << s_ for s_ in range(3) if 0 <= S * ox - 1 + s_ < W) for ox in range(OW)]
+        rm, sm = _tap_masks(H, W, S)
+        OH, OW = len(rm), len(sm)
         cls = {}
         for oy in range(OH):
             for ox in range(OW):
@@ -670,9 +690,7 @@ def _cell_classes(H, W, S):
     and the corner have taps in the padding).  The interior class comes first.  None when a class is not a rectangle."""
     key = (H, W, S)
     if key not in _CELL_CLASSES:
-        OH, OW = (H - 1) // S + 1, (W - 1) // S + 1
-        rm = [sum(1 << r for r in range(3) if 0 <= S * oy - 1 + r < H) for oy in range(OH)]
-        sm = [sum(1 << c for c in range(3) if 0 <= S * ox - 1 + c < W) for ox in range(OW)]
+        rm, sm = _tap_masks(H, W, S)
 
         def ranges(masks):
             out = {}
@@ -691,17 +709,6 @@ def _cell_classes(H, W, S):
             cls = [(7, 7, rr[7], cc[7])] + [(r_, c_, rr[r_], cc[c_]) for r_ in sorted(rr) for c_ in sorted(cc) if (r_, c_) != (7, 7)]
         _CELL_CLASSES[key] = cls
     return _CELL_CLASSES[key]
-
-
-def _chain_planes(V, Wf, out, T, K, N2, shift):
-    """out [T][N2] = sum over the 25 planes of V ([25][T][K] flat) x Wf [N2][25 K] (tap-major) + shift: launches of up to five planes
-    each, chained through the residual input (see rpn_composite: shorter fmaf chains, and a plane group stays inside the 2 GB window of
-    a buffer resource)."""
-    ppl = max(1, min(5, ((1 << 31) - (1 << 24)) // (T * K * 4)))
-    for p0 in range(0, 25, ppl):
-        npl = min(ppl, 25 - p0)
-        gemm_conv(V[p0 * T * K:], Wf[:, p0 * K:], out, B=1, H=npl, W=T, Cin=K, N=N2, kh=npl, kw=1, Ho=1, Wo=T, x_ld=K, w_ld=25 * K,
-                  shift=shift if p0 == 0 else None, residual=out if p0 else None, res_ld=N2 if p0 else None)
 
 
 def train_composite_ready(fm, block):
@@ -886,6 +893,17 @@ def train_composite_fallback(st, gy):
     return gy
 
 
+def _roi_tile_buf(device, n):
+    """(tile list int32 [n], its block counter int32 [1]) of the current lane, shared by every RoI phase whose list need not outlive
+    the launches that read it."""
+    key = (str(device), n, ops.LANE)
+    buf = _ROI_TILE_BUF.get(key)
+    if buf is None:
+        buf = _ROI_TILE_BUF[key] = (torch.empty((n,), device=device, dtype=torch.int32),
+                                    torch.zeros((1,), device=device, dtype=torch.int32))
+    return buf
+
+
 def lazy_state(fm):
     """The LazyMap of a demand-driven map (or None)."""
     hit = _LAZY.get(fm.data_ptr())
@@ -893,8 +911,7 @@ def lazy_state(fm):
 
 
 def lazy_pending(fm):
-    hit = _LAZY.get(fm.data_ptr())
-    return hit is not None and hit[1]() is not None
+    return lazy_state(fm) is not None
 
 
 def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
@@ -902,10 +919,9 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
     `roi_pool` reads).  rois [B,cap,4], n_roi device int32 [B] (or [1]: `ops.roi_counts`), fmap_hw: (h, w) of every pyramid
     level.  No-op for a map that is not deferred.  May be called any number of times on the same map (each RoI pooling calls it
     with its own RoIs): the operands live as long as the map."""
-    hit = _LAZY.get(fm.data_ptr())
-    if hit is None or hit[1]() is None:
+    st = lazy_state(fm)
+    if st is None:
         return
-    st = hit[0]
     x, U, bias = st.x, st.U, st.bias
     if x is None:
         raise RuntimeError('this demand-driven FPN map has been through its backward pass: its operands are gone and the tiles '
@@ -923,19 +939,15 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
     fw = (C.c_int * nl)(*[int(w) for _, w in fmap_hw])
     blocks_per_img = -(-((H + 1) // 2 * ((W + 1) // 2)) // 128)
     keep = st.keep and (st.sparse or st.overlap)  # a backward pass will want the lists
-    per_chunk = []
+    chunks = []
     for b0, nb, _ in st.chunks:
-        key = (str(x.device), nb * blocks_per_img * 128, ops.LANE)
+        n_list = nb * blocks_per_img * 128
         nr = n_roi[b0:b0 + nb]
         if keep:                                  # the backward pass reads the list again: a buffer of its own
-            tiles = torch.empty((key[1],), device=x.device, dtype=torch.int32)
+            tiles = torch.empty((n_list,), device=x.device, dtype=torch.int32)
             n_blocks = torch.zeros((1,), device=x.device, dtype=torch.int32)
         else:
-            buf = _ROI_TILE_BUF.get(key)
-            if buf is None:
-                buf = _ROI_TILE_BUF[key] = (torch.empty((key[1],), device=x.device, dtype=torch.int32),
-                                            torch.zeros((1,), device=x.device, dtype=torch.int32))
-            tiles, n_blocks = buf
+            tiles, n_blocks = _roi_tile_buf(x.device, n_list)
         check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, _ptr(st.skip), 0, _ptr(tiles),
                                   _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
         if st.lateral is not None:                # the input patches of these tiles first (16 pixels per listed tile)
@@ -951,7 +963,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
             if st.lateral is not None and st.lateral.ufold is not None and LAT_CELL_BWD and st.stride >= 5:
                 # the data gradient's list (tiles within a pixel of the windows) now, so that its length is known on the host when
                 # the backward pass sizes the compact operands of the lateral's RoI share
-                tiles_d = torch.empty((key[1],), device=x.device, dtype=torch.int32)
+                tiles_d = torch.empty((n_list,), device=x.device, dtype=torch.int32)
                 nbd = torch.zeros((1,), device=x.device, dtype=torch.int32)
                 check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, None, 1, _ptr(tiles_d), _ptr(nbd),
                                           _stream()), 'nbm_roi_tiles')
@@ -959,21 +971,10 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
                 host_d.copy_(nbd, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            per_chunk.append((tiles, host, ev, tiles_d, host_d))
+            chunks.append(RoiChunk(tiles, host, ev, tiles_d, host_d))
     if keep:                                      # the data gradient lists the tiles around these windows again
-        st.roi.append(per_chunk)
-        st.rois.append((rois, n_roi, nl, level, fh, fw))
+        st.rois.append(RoiPooling(rois, n_roi, nl, level, fh, fw, chunks))
     st.done += 1
-
-
-# The deferred lateral's OWN gradients from the consumer's backward pass: its pattern share rides in the cell-domain GEMMs (the
-# folded weights [U | alpha U W] give d/dt in the transform domain, the weight-gradient GEMMs already hold d/d(alpha U W)), its RoI
-# share runs on compact [tiles x 4 pixels] operands -- instead of three dense passes over the 18.9 GB gradient of the merged map
-LAT_CELL_BWD = os.environ.get('NBM_LAT_CELL_BWD', '1') != '0'
-# ... and then the only reader left of d/d(merged map) is the bilinear backward of the top-down merge: the RoI share stays in its
-# compact form (nbm_tiles_upsample_bilinear_bwd_add) and the map holds the pattern patches only, which lets that reader skip the rows
-# and columns between the patches (nbm_upsample_bilinear_bwd(pattern_stride): 61 % of 18.9 GB at B = 128)
-UPBWD_SPLIT = os.environ.get('NBM_UPBWD_SPLIT', '1') != '0'
 
 
 # ---- persistent gradient maps of a demand-driven level (training)
@@ -985,8 +986,6 @@ UPBWD_SPLIT = os.environ.get('NBM_UPBWD_SPLIT', '1') != '0'
 # consumer, exception, autograd accumulated something into it in place: its version counter moved) is filled completely at its next
 # `zero_acquire`.  Because the buffer is handed to autograd as a gradient, code that KEEPS that gradient beyond the backward pass
 # (`retain_grad()` on the FPN map) sees it change in the next step: set NBM_ZERO_POOL=0 for that.
-ZERO_POOL = os.environ.get('NBM_ZERO_POOL', '1') != '0'
-ZERO_POOL_CHECK = os.environ.get('NBM_ZERO_POOL_CHECK', '0') == '1'      # tests: verify the buffer after every recycle (synchronises)
 _ZERO_POOL = {}
 
 
@@ -1018,6 +1017,12 @@ def zero_acquire(shape, device, tag):
 
 def zero_note(e, fn):
     e['zeroers'].append(fn)
+
+
+def _note_zero_tiles(e, ptr, nb, H, W, C_, tiles, n, n_blocks):
+    """Undo of a RoI share in a persistent gradient map (pool entry `e`): the n listed tiles (or `n_blocks` blocks of them, a device
+    counter) of the nb images [H,W,C_] at address `ptr` are zeroed when the map is recycled."""
+    zero_note(e, lambda: check(lib().nbm_zero_tiles(ptr, nb, H, W, C_, _ptr(tiles), n, _ptr(n_blocks), _stream()), 'nbm_zero_tiles'))
 
 
 def zero_recycle(t):
@@ -1118,7 +1123,7 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
     # (LAT_CELL_BWD above) and left in st.lateral.grads for the lateral's own backward node
     lt = st.lateral
     do_lat = bool(lateral_grads and LAT_CELL_BWD and cell and not overlap and lt is not None and lt.ufold is not None and
-                  all(pc[3] is not None for per_chunk in st.roi for pc in per_chunk) and len(st.roi) == len(st.rois) and
+                  all(ch.tiles_d is not None for pooling in st.rois for ch in pooling.chunks) and
                   len(st.rois) <= 1)          # RoI shares are ADDED: a tile listed by two poolings would count twice
     if do_lat:
         Cin = lt.t.shape[-1]
@@ -1164,11 +1169,8 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
                     T = vg.shape[1]
                     if do_lat:
                         mp = K
-                        M, _ = ops._wino_scratch(g.device, 25 * T * K, 0)
-                        gemm_conv(vg, Ud, M, B=1, H=T, W=1, Cin=N, N=K, groups=25, x_gs=T * N, w_gs=K * N, y_gs=T * K)
-                    else:
-                        M, _ = ops._wino_scratch(g.device, 25 * T * C_, 0)
-                        gemm_conv(vg, Ucell, M, B=1, H=T, W=1, Cin=N, N=C_, groups=25, x_gs=T * N, w_gs=C_ * N, y_gs=T * C_)
+                    M, _ = ops._wino_scratch(g.device, 25 * T * mp, 0)
+                    gemm_conv(vg, Ud if do_lat else Ucell, M, B=1, H=T, W=1, Cin=N, N=mp, groups=25, x_gs=T * N, w_gs=mp * N, y_gs=T * mp)
             finally:
                 ops._PROFILE_LABEL = global_label
             if do_lat:            # d/d(merged map) patches (+ their sum = pattern share of the lateral's bias gradient), d/dt patches
@@ -1184,16 +1186,16 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
             pat = wino23_pattern(nb, H, W, st.stride, g.device, dilate=1)
             _wino23_tiles_run(g[b0:b0 + nb], Ut, None, gx.data_ptr() + b0 * img_bytes, pat.tiles, None, pat.n_eff, 'wino23-dgrad',
                               pat.blk_info)
-        for si, (rois, n_roi, nl, level, fh, fw) in enumerate(st.rois):          # one entry per RoI pooling that read the map
+        for pooling in st.rois:                       # one entry per RoI pooling that read the map
             if do_lat:
                 # RoI share, kept apart from the pattern share: g with its pattern pixels read as zeros through the listed kernel into a
                 # COMPACT [tiles][2][2][C] operand; added to the map (the bilinear backward reads it there), and the lateral's three
                 # gradients of these pixels from compact operands (a few % of the map)
-                _, _, ev, tl, host_d = st.roi[si][ci]
-                ev.synchronize()                          # recorded during the forward pass: long done
-                n = int(host_d.item()) * 128
+                ch = pooling.chunks[ci]
+                ch.event.synchronize()                    # recorded during the forward pass: long done
+                n = int(ch.host_d.item()) * 128
                 if n:
-                    tl = tl[:n]
+                    tl = ch.tiles_d[:n]
                     gx_p, dt_p = C.c_void_p(gx.data_ptr() + b0 * img_bytes), C.c_void_p(dt.data_ptr() + b0 * dt_img_bytes)
                     Gc = torch.zeros((n * 4, C_), device=g.device, dtype=torch.float32)
                     # (composed reader: the pattern pixels of g hold the RoI pooling's share only -- nothing is masked)
@@ -1213,24 +1215,18 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
                     conv_wgrad(Gc, tc, gw_roi, B=1, H=n * 4, W=1, Cin=Cin, N=C_, alpha=float(lt.alpha), bias_grad=gb_lat)
                     for pl, (p_, c_) in ((None if split else pool, (gx_p, C_)), (dt_pool, (dt_p, Cin))):
                         if pl is not None:
-                            zero_note(pl, lambda p_=p_, c_=c_, nb_=nb, tl_=tl, n_=n: check(
-                                lib().nbm_zero_tiles(p_, nb_, H, W, c_, _ptr(tl_), n_, None, _stream()), 'nbm_zero_tiles'))
+                            _note_zero_tiles(pl, p_, nb, H, W, c_, tl, n, None)
                 continue
-            key = (str(g.device), nb * blocks_per_img * 128, ops.LANE)
-            buf = _ROI_TILE_BUF.get(key)
-            if buf is None:
-                buf = _ROI_TILE_BUF[key] = (torch.empty((key[1],), device=g.device, dtype=torch.int32),
-                                            torch.zeros((1,), device=g.device, dtype=torch.int32))
-            tiles, n_blocks = buf
-            check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(n_roi[b0:b0 + nb]), nb, rois.shape[1], nl, level,
-                                      fh, fw, None if cell else _ptr(pat.full), 1, _ptr(tiles), _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
+            tiles, n_blocks = _roi_tile_buf(g.device, nb * blocks_per_img * 128)
+            check(lib().nbm_roi_tiles(_ptr(pooling.rois[b0:b0 + nb]), _ptr(pooling.n_roi[b0:b0 + nb]), nb, pooling.rois.shape[1],
+                                      pooling.n_levels, pooling.level, pooling.fh, pooling.fw, None if cell else _ptr(pat.full), 1,
+                                      _ptr(tiles), _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
             # composed reader: g holds the RoI pooling's share only (pattern pixels included), ADDED to the cell patches
             _wino23_tiles_run(g[b0:b0 + nb], Ut, None, gx.data_ptr() + b0 * img_bytes, tiles, n_blocks, None, 'wino23-dgrad-rois',
                               skip_pattern=st.stride if (overlap and comp is None) else 0, accumulate=overlap or comp is not None)
             if pool is not None:
                 tl, nbk = tiles.clone(), n_blocks.clone()          # the list buffer is shared by all chunks / levels
-                zero_note(pool, lambda p_=gx.data_ptr() + b0 * img_bytes, nb_=nb, tl_=tl, nbk_=nbk: check(
-                    lib().nbm_zero_tiles(C.c_void_p(p_), nb_, H, W, C_, _ptr(tl_), tl_.numel(), _ptr(nbk_), _stream()), 'nbm_zero_tiles'))
+                _note_zero_tiles(pool, C.c_void_p(gx.data_ptr() + b0 * img_bytes), nb, H, W, C_, tl, tl.numel(), nbk)
     if do_lat:
         if dt_pool is not None and ZERO_POOL_CHECK:
             dt_pool['check'] = lambda buf, s_=st.stride: _check_zero_outside_patches(buf, s_)
@@ -1243,8 +1239,7 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
                     check(lib().nbm_tiles_scatter_add(p_, nb_, H, W, C_, _ptr(tl_), tl_.numel(), None, _ptr(Gc_), _stream()),
                           'nbm_tiles_scatter_add')
                     if pool is not None and pool['buf'].data_ptr() == gy.data_ptr():
-                        zero_note(pool, lambda p_=p_, nb_=nb_, tl_=tl_: check(
-                            lib().nbm_zero_tiles(p_, nb_, H, W, C_, _ptr(tl_), tl_.numel(), None, _stream()), 'nbm_zero_tiles'))
+                        _note_zero_tiles(pool, p_, nb_, H, W, C_, tl_, tl_.numel(), None)
             lt.grads.update(up_share=shares, pat_stride=st.stride, gx_ptr=gx.data_ptr(), complete=complete)
     return gx
 
@@ -1300,12 +1295,12 @@ def conv3x3_winograd_wgrad_tiles(st, x, g, want_bias=False, cell=None):
             conv_wgrad(vg, Vx, dUc, B=1, H=T, W=1, Cin=K, N=N, groups=25, g_gs=T * N, x_gs=T * K, out_gs=N * K)
             st.vg.pop(ci, None)
         parts = []
-        for per_chunk in st.roi:                    # one entry per RoI pooling that read the map
-            tiles, host, ev = per_chunk[ci][:3]
-            ev.synchronize()                        # recorded during the forward pass: long done
-            n = int(host.item()) * 128
+        for pooling in st.rois:                     # one entry per RoI pooling that read the map
+            ch = pooling.chunks[ci]
+            ch.event.synchronize()                  # recorded during the forward pass: long done
+            n = int(ch.host.item()) * 128
             if n:
-                parts.append(tiles[:n])
+                parts.append(ch.tiles[:n])
         if parts:
             if len(parts) == 1:
                 roi = parts[0]

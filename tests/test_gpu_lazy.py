@@ -272,7 +272,8 @@ def test_weight_gradient_over_the_listed_tiles_equals_the_dense_one(cell):
     # pixels with a reader: the pattern pixels + every pixel of the tiles under the RoIs (re-derived from the kept RoI list)
     TH, TW = (H + 1) // 2, (W + 1) // 2
     m = ~torch.isnan(y[..., 0])                      # the map was NaN-poisoned: written == has a reader
-    tiles, host, ev = st.roi[0][0][:3]
+    ch = st.rois[0].chunks[0]
+    tiles, host, ev = ch.tiles, ch.host, ch.event
     ev.synchronize()
     ids = tiles[:int(host.item()) * 128]
     assert int((ids >= 0).sum()) > 0

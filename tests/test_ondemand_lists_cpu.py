@@ -98,8 +98,10 @@ def test_pinned_counters_return_to_the_pool_when_the_map_dies():
     before = len(ondemand._PINNED_FREE)
     st = ondemand.LazyMap(None, None, None, 8)
     hosts = [torch.zeros(1, dtype=torch.int32) for _ in range(5)]
-    st.roi.append([(None, hosts[0], None, None, None), (None, hosts[1], None, 'tiles_d', hosts[2])])
-    st.roi.append([(None, hosts[3], None), (None, hosts[4], None, None, None)])          # the 3-tuples of the older layout too
+    def pooling(*chunks):
+        return ondemand.RoiPooling(None, None, 5, 0, None, None, [ondemand.RoiChunk(None, *c) for c in chunks])
+    st.rois.append(pooling((hosts[0], None, None, None), (hosts[1], None, 'tiles_d', hosts[2])))     # the second chunk has a dilated list
+    st.rois.append(pooling((hosts[3], None, None, None), (hosts[4], None, None, None)))
     del st
     gc.collect()
     got = ondemand._PINNED_FREE[before:]

@@ -80,3 +80,16 @@ def test_composed_weights_reproduce_the_chain_of_layers(geom):
     raw = pre * torch.sigmoid(pre)
     bad = (raw - ref).abs() > 1e-4 * max(1.0, float(ref.abs().max()))
     assert bool(bad.any()) and int(bad.any(1).any(0).sum()) <= border_cells
+
+
+def test_cell_classes_and_border_classes_name_the_same_cells():
+    """The two groupings of the cell grid by (row mask, column mask) -- rectangles for the training composition (`_cell_classes`), index
+    tensors for the evaluation one (`_border_classes`) -- hold the same non-interior classes with the same cells."""
+    for H, W, S in [(188, 512, 8), (47, 66, 8), (94, 256, 4), (25, 33, 3), (9, 10, 5)]:
+        OW = (W - 1) // S + 1
+        rect = {(r_, s_): {oy * OW + ox for oy in range(*ry) for ox in range(*rx)}
+                for r_, s_, ry, rx in ondemand._cell_classes(H, W, S) if (r_, s_) != (7, 7)}
+        border = {(r_, s_): set(idx.tolist()) for r_, s_, _, _, idx, _ in ondemand._border_classes(1, H, W, S, 'cpu')}
+        assert rect and set(rect) == set(border), (H, W, S)
+        assert rect == border, (H, W, S)
+    assert ondemand._cell_classes(8, 8, 8) is None            # one cell, a tap in the padding: no interior class
