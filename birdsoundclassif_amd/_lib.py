@@ -62,6 +62,14 @@ class BwdDesc(C.Structure):
                 ('mask_bits', C.c_void_p)]
 
 
+class GemmPlan(C.Structure):
+    """struct nbm_gemm_plan_t (include/nbm_hip.h)."""
+    _fields_ = [('name', C.c_char_p), ('rc', C.c_int), ('kernel', C.c_int), ('grid', C.c_int * 3), ('block', C.c_int),
+                ('m_tiles', C.c_int), ('n_tiles', C.c_int), ('vec_epi', C.c_int), ('fast', C.c_int), ('slices', C.c_int),
+                ('phased', C.c_int), ('ph_tiles', C.c_int * 4), ('splits', C.c_int), ('k_chunk', C.c_int),
+                ('plain', C.c_int), ('b_generic', C.c_int), ('narrow_m', C.c_int), ('halves', C.c_int)]
+
+
 _P, _I, _L, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 # name -> argtypes (restype is int unless noted); must list every symbol of include/nbm_hip.h
@@ -105,6 +113,7 @@ SIGNATURES = {
     # ---- training path
     'nbm_conv_dgrad': [C.POINTER(BwdDesc), _P],
     'nbm_conv_wgrad': [C.POINTER(BwdDesc), _P],
+    'nbm_gemm_plan': [_I, _P, C.POINTER(GemmPlan)],
     'nbm_relu_bwd': [_P, _P, _P, _L, _P],
     'nbm_silu_bwd': [_P, _P, _P, _L, _P],
     'nbm_axpby': [_P, _P, _P, _F, _F, _L, _L, _P],

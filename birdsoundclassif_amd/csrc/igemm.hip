@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include "nbm_common.h"
 #include "igemm_params.h"
+#include "igemm_plan.h"
 #include <type_traits>
 
 namespace {
@@ -509,51 +510,15 @@ __global__ __launch_bounds__(WAVES * 64, 1) void stream1x1_kernel(const StreamPa
   }
 }
 
-template <int K32, int NT, int NTG, int WAVES, int WG_PER_CU>
-int launch_stream(const StreamParams& p, hipStream_t st, int slices = 1) {
-  const int wgs = (p.m_tiles + WAVES - 1) / WAVES;
-  int gx = 256 * WG_PER_CU / slices;                    // the persistent grid is shared by the slices
-  if (gx < 1) gx = 1;
-  hipLaunchKernelGGL((stream1x1_kernel<K32, NT, NTG, WAVES>), dim3(wgs < gx ? wgs : gx, slices), dim3(WAVES * 64), 0, st, p);
-  return nbm_launch_status();
-}
-
-template <int BM, int BN, int WM, int WN, int AMODE, int EPI>
-int launch(const IgemmParams& p, int groups, hipStream_t st) {
-  dim3 grid(p.m_tiles * p.n_tiles, 1, groups);
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, AMODE, EPI>), grid, dim3(256), 0, st, p);
-  return nbm_launch_status();
-}
-
-int launch_s1(const IgemmParams& p, int groups, hipStream_t st) {
-  dim3 grid(p.m_tiles * p.n_tiles, 1, groups);
-  hipLaunchKernelGGL((igemm_kernel<128, 128, 64, 64, A_FAST, EPI_STD, 1>), grid, dim3(256), 0, st, p);
-  return nbm_launch_status();
-}
-
-int launch_s1_rows(const IgemmParams& p, hipStream_t st) {
-  const int mt = p.rows_blocks ? (p.m_tiles + 7) / 8 * 8 : p.m_tiles;
-  dim3 grid(mt * p.n_tiles, 1, 1);
-  hipLaunchKernelGGL((igemm_kernel<128, 128, 64, 64, A_FAST, EPI_STD, 1, true>), grid, dim3(256), 0, st, p);
-  return nbm_launch_status();
-}
-
 }  // namespace
 
+using namespace nbm_igemm;
+
 extern "C" int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream) {
-  if (!d || !d->x || !d->w || !d->y) return NBM_EINVAL;
-  if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->N <= 0 || d->kh <= 0 || d->kw <= 0 ||
-      d->stride <= 0 || d->Ho <= 0 || d->Wo <= 0 || d->groups <= 0)
-    return NBM_EINVAL;
-  // host-side shape check: the output geometry must be the one the gather assumes
-  if ((d->H + 2 * d->pad - d->kh) / d->stride + 1 != d->Ho || (d->W + 2 * d->pad - d->kw) / d->stride + 1 != d->Wo)
-    return NBM_EINVAL;
-  if (d->x_ld < d->Cin || d->y_ld < d->N || (d->residual && d->res_ld < d->N)) return NBM_EINVAL;
-  // An output width 64 past a multiple of 128 (the cell-domain data-gradient planes of the deferred lateral: 256 -> 448): the last 128-wide
-  // tile would be half padding -- the first N - 64 channels on 128-wide tiles, the last 64 on the 64-wide kernel.  Every output element is the
-  // same sum in the same order either way (round 5; weight-gradient twin: nbm_conv_wgrad).
-  if (d->N > 128 && (d->N & 127) == 64 && !d->rows && !d->up && !d->bits_out && !d->shift_per_row && (d->Cin % BK) == 0 &&
-      d->kh * d->kw * d->Cin > 256) {
+  if (!d) return NBM_EINVAL;
+  const GemmPlan pl = plan_fwd(*d, read_gemm_switches(0));
+  if (pl.rc) return pl.rc;
+  if (pl.halves) {               // N is 64 past a multiple of 128: the first N - 64 channels, then the last 64 (see plan_fwd)
     nbm_gemm_desc a = *d, b = *d;
     const int n0 = d->N - 64;
     a.N = n0;
@@ -567,108 +532,65 @@ extern "C" int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream) {
     const int rc = nbm_gemm_conv(&a, stream);
     return rc ? rc : nbm_gemm_conv(&b, stream);
   }
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
+  hipStream_t st = (hipStream_t)stream;
+  const int M = d->B * d->Ho * d->Wo;
+  if (pl.slices) {               // the stream1x1 forms
+    const StreamParams sp{d->x, d->w, d->y, d->scale, d->shift, d->residual, M, d->x_ld, d->w_ld, d->y_ld, d->res_ld, pl.m_tiles,
+                          d->alpha, d->act, d->bits_out, d->N >> 5};
+    switch (pl.kernel) {
+      case K_STREAM_64_256: hipLaunchKernelGGL((stream1x1_kernel<2, 8, 4, 8>), grid, block, 0, st, sp); break;
+      case K_STREAM_64_64: hipLaunchKernelGGL((stream1x1_kernel<2, 2, 2, 8>), grid, block, 0, st, sp); break;
+      case K_STREAM_128_SLICED: hipLaunchKernelGGL((stream1x1_kernel<4, 4, 4, 8>), grid, block, 0, st, sp); break;
+      default: hipLaunchKernelGGL((stream1x1_kernel<8, 2, 2, 8>), grid, block, 0, st, sp); break;      // K_STREAM_256_64, K_STREAM_256_SLICED
+    }
+    return nbm_launch_status();
+  }
   IgemmParams p{};
   p.x = d->x; p.w = d->w; p.y = d->y; p.scale = d->scale; p.shift = d->shift; p.residual = d->residual;
   p.x_gs = d->x_gs; p.w_gs = d->w_gs; p.y_gs = d->y_gs; p.res_gs = d->res_gs;
-  p.M = d->B * d->Ho * d->Wo; p.N = d->N; p.K = d->kh * d->kw * d->Cin;
+  p.M = M; p.N = d->N; p.K = d->kh * d->kw * d->Cin;
   p.nk = (p.K + BK - 1) / BK;
   p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad = d->pad;
   p.Ho = d->Ho; p.Wo = d->Wo; p.HoWo = d->Ho * d->Wo;
   p.fd_howo = nbm_fastdiv_make((unsigned)p.HoWo); p.fd_wo = nbm_fastdiv_make((unsigned)p.Wo);
   p.x_ld = d->x_ld; p.w_ld = d->w_ld; p.y_ld = d->y_ld; p.res_ld = d->res_ld;
   p.alpha = d->alpha; p.act = d->act; p.shift_per_row = d->shift_per_row;
-  if (p.w_ld < p.nk * BK) return NBM_EINVAL;  // every W row must hold nk*32 readable floats
-  if (d->mask) {
-    if (d->rows || d->groups != 1 || d->mask_ld < d->N) return NBM_EUNSUPPORTED;
-    p.mask = d->mask; p.mask_ld = d->mask_ld;
-  }
-  p.vec_epi = ((d->N & 3) == 0 && (d->y_ld & 3) == 0 && (d->y_gs & 3) == 0 && nbm_aligned16(d->y) &&
-               (!d->residual || ((d->res_ld & 3) == 0 && (d->res_gs & 3) == 0 && nbm_aligned16(d->residual))) &&
-               (!d->scale || nbm_aligned16(d->scale)) && (!d->shift || d->shift_per_row || nbm_aligned16(d->shift)) &&
-               (!d->mask || ((d->mask_ld & 3) == 0 && nbm_aligned16(d->mask))))
-                  ? 1 : 0;
-  if ((d->w_ld & 3) || (d->w_gs & 3) || !nbm_aligned16(d->w)) return NBM_EALIGN;
-  if (d->bits_out) {              // (y > 0) bits: written by the vector epilogue, whole 32-channel words
-    if (!p.vec_epi || (d->N & 31) || d->groups != 1 || d->rows) return NBM_EUNSUPPORTED;
-    p.bits_out = d->bits_out;
-  }
+  p.m_tiles = pl.m_tiles; p.n_tiles = pl.n_tiles; p.vec_epi = pl.vec_epi;
+  if (d->mask) { p.mask = d->mask; p.mask_ld = d->mask_ld; }
+  p.bits_out = d->bits_out;
   if (d->up) {
-    if (!p.vec_epi || d->groups != 1 || d->up_H <= 0 || d->up_W <= 0 || !nbm_aligned16(d->up)) return NBM_EUNSUPPORTED;
     p.up = d->up; p.up_H = d->up_H; p.up_W = d->up_W;
     p.up_sh = d->Ho > 1 ? (float)(d->up_H - 1) / (float)(d->Ho - 1) : 0.f;
     p.up_sw = d->Wo > 1 ? (float)(d->up_W - 1) / (float)(d->Wo - 1) : 0.f;
   }
-  const bool fast = (d->Cin % BK) == 0 && (d->x_ld & 3) == 0 && (d->x_gs & 3) == 0 && nbm_aligned16(d->x);
-  hipStream_t st = (hipStream_t)stream;
-  const int BM = 128;
-  p.m_tiles = (p.M + BM - 1) / BM;
-  if (d->rows) {                  // listed rows: the short-K 1x1 variant only
-    if (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0 || d->groups != 1 || !fast || !p.vec_epi || d->shift_per_row ||
-        p.nk > 8 || d->N <= 64 || (d->rows_mode != 1 && d->rows_mode != 2) || d->rows_count <= 0 || (d->rows_count % 128))
-      return NBM_EUNSUPPORTED;
-    if (d->rows_mode == 2 && (d->rows_TH != (d->H + 1) / 2 || d->rows_TW != (d->W + 1) / 2)) return NBM_EINVAL;
-    if (2ll * d->H * d->W * d->x_ld * 4 > 0x7fffffffll) return NBM_EUNSUPPORTED;
+  if (d->rows) {
     p.rows = d->rows; p.rows_blocks = d->rows_blocks; p.rows_mode = d->rows_mode; p.rows_TH = d->rows_TH; p.rows_TW = d->rows_TW;
     p.fd_rows_thw = nbm_fastdiv_make((unsigned)(d->rows_TH * d->rows_TW)); p.fd_rows_tw = nbm_fastdiv_make((unsigned)d->rows_TW);
     p.M = d->rows_count;
-    p.m_tiles = p.M / BM;
-    p.n_tiles = (d->N + 127) / 128;
-    return launch_s1_rows(p, st);
   }
-  // streaming form for 1x1 / stride 1 layers whose weights fit LDS (see stream1x1_kernel)
-  const char* stream_env = getenv("NBM_STREAM1X1");          // read per call: the parity test flips it inside one process
-  if (!(stream_env && stream_env[0] == '0') && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->groups == 1 && fast && p.vec_epi && !d->up && !d->mask &&
-      !d->shift_per_row && (d->N % 32) == 0 && p.M >= 8192) {
-    StreamParams sp{d->x, d->w, d->y, d->scale, d->shift, d->residual, p.M, d->x_ld, d->w_ld, d->y_ld, d->res_ld, (p.M + 31) / 32,
-                    d->alpha, d->act, d->bits_out, d->N >> 5};
-    const int k32 = d->Cin / 32, nt = d->N / 32;
-    // 64 -> 256 without a residual is write-bound and gains nothing (0.78 ms either way at B = 64): tiled kernel
-    if (k32 == 2 && nt == 8 && d->residual) return launch_stream<2, 8, 4, 8, 1>(sp, st);
-    if (k32 == 2 && nt == 2) return launch_stream<2, 2, 2, 8, 2>(sp, st);
-    if (k32 == 8 && nt == 2) return launch_stream<8, 2, 2, 8, 1>(sp, st);
-    // wider layers in slices of N
-    if (d->residual) {
-      if (k32 == 4 && nt % 4 == 0 && nt <= 32) return launch_stream<4, 4, 4, 8, 1>(sp, st, nt / 4);      // 128 -> 512: 4 slices of 128
-      if (k32 == 8 && nt % 2 == 0 && nt <= 64) return launch_stream<8, 2, 2, 8, 1>(sp, st, nt / 2);      // 256 -> 1024: 16 slices of 64
-    }
+  switch (pl.kernel) {
+    case K_FWD_ROWS: hipLaunchKernelGGL((igemm_kernel<128, 128, 64, 64, A_FAST, EPI_STD, 1, true>), grid, block, 0, st, p); break;
+    case K_FWD_SPLIT_R0: case K_FWD_SPLIT_R2: case K_FWD_SPLIT_R4: return split_launch(p, pl, st);
+    case K_FWD_H16: return h16_launch(p, pl, st);
+    case K_FWD_128_S1: hipLaunchKernelGGL((igemm_kernel<128, 128, 64, 64, A_FAST, EPI_STD, 1>), grid, block, 0, st, p); break;
+    case K_FWD_128_FAST: hipLaunchKernelGGL((igemm_kernel<128, 128, 64, 64, A_FAST, EPI_STD>), grid, block, 0, st, p); break;
+    case K_FWD_128_GENERIC: hipLaunchKernelGGL((igemm_kernel<128, 128, 64, 64, A_GENERIC, EPI_STD>), grid, block, 0, st, p); break;
+    case K_FWD_64_S1: hipLaunchKernelGGL((igemm_kernel<128, 64, 64, 32, A_FAST, EPI_STD, 1>), grid, block, 0, st, p); break;
+    case K_FWD_64_FAST: hipLaunchKernelGGL((igemm_kernel<128, 64, 64, 32, A_FAST, EPI_STD>), grid, block, 0, st, p); break;
+    case K_FWD_64_GENERIC: hipLaunchKernelGGL((igemm_kernel<128, 64, 64, 32, A_GENERIC, EPI_STD>), grid, block, 0, st, p); break;
+    case K_FWD_32_FAST: hipLaunchKernelGGL((igemm_kernel<128, 32, 32, 32, A_FAST, EPI_STD>), grid, block, 0, st, p); break;
+    case K_FWD_32_GENERIC: hipLaunchKernelGGL((igemm_kernel<128, 32, 32, 32, A_GENERIC, EPI_STD>), grid, block, 0, st, p); break;
+    default: return NBM_EINVAL;
   }
-  if (d->N > 64) {
-    p.n_tiles = (d->N + 127) / 128;
-    // deep K on the bf16 matrix pipe through split fp32 operands (igemm_split.hip); NBM_SPLIT_BF16=0 keeps the fp32 instruction.
-    // Read per call: the parity tests flip it inside one process.  The choice depends on the LAYER (K, N), never on the number of rows:
-    // a clip's result must not depend on how many clips share its batch (the two kernels sum in different orders).
-    const char* split_env = getenv("NBM_SPLIT_BF16");
-    if (split_env && split_env[0] == '1' && fast && p.vec_epi && p.nk >= 9 && d->kh * d->kw < 63)
-      return nbm_igemm::split_launch(p, d->groups, st);
-    // deep K: half-step LDS stages, three workgroups per CU (igemm_h16.hip: the same products in the same order as the two-stage kernel below,
-    // 2-14 % faster launch by launch at B = 64, scripts/h16_probe.py).  NBM_H16 = 0: the two-stage kernel.  From 9 K-steps up; up to 8 the
-    // single-stage kernel below stays
-    const char* h16_env = getenv("NBM_H16");                   // read per call: the parity test flips it inside one process
-    if (!(h16_env && atoi(h16_env) == 0) && fast && p.vec_epi && p.nk >= 9 && d->kh * d->kw < 63) return nbm_igemm::h16_launch(p, d->groups, st);
-    // short K and a 16-byte epilogue: the three-workgroups-per-CU variant (see the template comment)
-    if (fast && p.vec_epi && p.nk <= 8)
-      return launch_s1(p, d->groups, st);
+  return nbm_launch_status();
+}
 
-    return fast ? launch<128, 128, 64, 64, A_FAST, EPI_STD>(p, d->groups, st)
-                : launch<128, 128, 64, 64, A_GENERIC, EPI_STD>(p, d->groups, st);
-  } else if (d->N > 32) {
-    p.n_tiles = 1;
-    // (NEGATIVE, round 5: 256 x 64 tiles with a 64 x 64 patch per wave -- the fragment reuse of the 128 x 128 kernel -- on the layer1 3x3
-    // 64 -> 64 @94x256: two LDS stages / one workgroup per CU 1.30 ms against 1.14 at B = 64, one stage / two workgroups per CU 1.15:
-    // the 64-wide tile's time is not its LDS reads per MFMA)
-    // single LDS stage / three workgroups per CU for the 64-wide tile up to K = 32 * 20: this tile spends half the
-    // MFMA cycles per K-step of the 128-wide one, so its prologue / epilogue weigh double and the third workgroup pays up to K = 576 (layer1's
-    // 3x3 64 -> 64 @94x256: 1.075 -> 0.99 ms at B = 64, 2.05 -> 1.83 at B = 128; same K order, same bits)
-    if (fast && p.vec_epi && p.nk <= 20) {
-      dim3 grid(p.m_tiles * p.n_tiles, 1, d->groups);
-      hipLaunchKernelGGL((igemm_kernel<128, 64, 64, 32, A_FAST, EPI_STD, 1>), grid, dim3(256), 0, st, p);
-      return nbm_launch_status();
-    }
-    return fast ? launch<128, 64, 64, 32, A_FAST, EPI_STD>(p, d->groups, st)
-                : launch<128, 64, 64, 32, A_GENERIC, EPI_STD>(p, d->groups, st);
-  } else {
-    p.n_tiles = 1;
-    return fast ? launch<128, 32, 32, 32, A_FAST, EPI_STD>(p, d->groups, st)
-                : launch<128, 32, 32, 32, A_GENERIC, EPI_STD>(p, d->groups, st);
-  }
+// The plan alone, nothing launched and no HIP call: see include/nbm_hip.h.
+extern "C" int nbm_gemm_plan(int kind, const void* desc, nbm_gemm_plan_t* out) {
+  if (!desc || !out || kind < 0 || kind > 2) return NBM_EINVAL;
+  const GemmSwitches sw = read_gemm_switches(kind);
+  *out = kind == 0 ? plan_fwd(*(const nbm_gemm_desc*)desc, sw)
+         : kind == 1 ? plan_dgrad(*(const nbm_bwd_desc*)desc, sw) : plan_wgrad(*(const nbm_bwd_desc*)desc, sw);
+  return out->rc;
 }

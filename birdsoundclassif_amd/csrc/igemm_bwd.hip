@@ -695,13 +695,10 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
 }  // namespace
 
 
-static int fill_common(const nbm_bwd_desc* d, BwdParams& p) {
-  if (!d || !d->g || !d->out) return NBM_EINVAL;
-  if (d->B <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->N <= 0 || d->kh <= 0 || d->kw <= 0 || d->stride <= 0 ||
-      d->groups <= 0 || d->kh * d->kw > 64)
-    return NBM_EINVAL;
-  if ((d->H + 2 * d->pad - d->kh) / d->stride + 1 != d->Ho || (d->W + 2 * d->pad - d->kw) / d->stride + 1 != d->Wo)
-    return NBM_EINVAL;
+using namespace nbm_igemm;
+
+static BwdParams fill_common(const nbm_bwd_desc* d, const GemmPlan& pl) {
+  BwdParams p{};
   p.g = d->g; p.w = d->w; p.x = d->x; p.out = d->out;
   p.a_scale = d->a_scale; p.row_scale = d->row_scale; p.residual = d->residual; p.mask = d->mask;
   p.residual2 = d->residual2; p.res2_ld = d->res2_ld;
@@ -712,178 +709,88 @@ static int fill_common(const nbm_bwd_desc* d, BwdParams& p) {
   p.g_ld = d->g_ld; p.w_ld = d->w_ld; p.x_ld = d->x_ld; p.out_ld = d->out_ld; p.res_ld = d->res_ld; p.mask_ld = d->mask_ld;
   p.alpha = d->alpha;
   p.bias_grad = d->bias_grad;
-  return NBM_OK;
+  p.m_tiles = pl.m_tiles; p.n_tiles = pl.n_tiles;
+  return p;
 }
 
 extern "C" int nbm_conv_dgrad(const nbm_bwd_desc* d, void* stream) {
-  BwdParams p{};
-  int rc = fill_common(d, p);
-  if (rc) return rc;
-  if (!d->w) return NBM_EINVAL;
-  // G rows must hold ceil(N/32)*32 readable floats (zero padded), 16-byte aligned; W rows are read along c
-  if ((d->g_ld & 3) || d->g_ld < ((d->N + 31) / 32) * 32 || (d->Cin & 3) || (d->w_ld & 3) || (d->g_gs & 3) || (d->w_gs & 3) ||
-      !nbm_aligned16(d->g) || !nbm_aligned16(d->w) || (d->a_scale && !nbm_aligned16(d->a_scale)))
-    return NBM_EALIGN;
-  if (d->out_ld < d->Cin || (d->residual && d->res_ld < d->Cin) || (d->mask && d->mask_ld < d->Cin)) return NBM_EINVAL;
-  if (d->residual2 && (d->stride != 1 || d->groups != 1 || d->res2_ld < d->Cin)) return NBM_EINVAL;
-  if (d->a_scale && (d->N & 31)) return NBM_EINVAL;
-  if (d->mask_bits) {                    // the ReLU mask as bits: whole 32-channel words, one group
-    if ((d->Cin & 31) || d->groups != 1) return NBM_EUNSUPPORTED;
-    p.mask_bits = d->mask_bits;
-  }
-  // the gather window of one 128-row tile (+ one image boundary) must stay inside the 2 GB buffer resource
-  {
-    const long long row = (long long)d->Wo * d->g_ld * 4;                  // bytes per G image row
-    const long long span = (d->W == 1 && d->kh == 1) ? 130ll * d->g_ld * 4   // plain GEMM: 128 consecutive rows
-                                                      : (d->kh + 130) * row + (long long)d->Ho * row;
-    if (span > 0x70000000ll) return NBM_EUNSUPPORTED;
-  }
+  if (!d) return NBM_EINVAL;
+  const GemmPlan pl = plan_dgrad(*d, read_gemm_switches(1));
+  if (pl.rc) return pl.rc;
+  BwdParams p = fill_common(d, pl);
+  p.mask_bits = d->mask_bits;
   p.M = d->B * d->H * d->W;
   p.w_row = d->w_ld;
-  p.vec_epi = ((d->out_ld & 3) == 0 && (d->out_gs & 3) == 0 && nbm_aligned16(d->out) &&
-               (!d->residual || ((d->res_ld & 3) == 0 && (d->res_gs & 3) == 0 && nbm_aligned16(d->residual))) &&
-               (!d->mask || ((d->mask_ld & 3) == 0 && nbm_aligned16(d->mask))) &&
-               (!d->residual2 || ((d->res2_ld & 3) == 0 && nbm_aligned16(d->residual2)))) ? 1 : 0;
-  p.m_tiles = (p.M + 127) / 128;
+  p.vec_epi = pl.vec_epi;
   p.fd_st = nbm_fastdiv_make((unsigned)d->stride);
   p.fd_HW = p.fd_hw[0] = nbm_fastdiv_make((unsigned)(d->H * d->W));
   p.fd_W = p.fd_w[0] = nbm_fastdiv_make((unsigned)d->W);
-  if (d->stride == 2) {                  // group the M tiles by parity class (see igemm_nn_kernel)
-    p.phased = 1;
-    int tmax = 0;
+  p.phased = pl.phased;
+  if (pl.phased) {                       // the M tiles grouped by parity class (see igemm_nn_kernel)
     for (int ph = 0; ph < 4; ++ph) {
       const int y0 = ((ph >> 1) + d->pad) & 1, x0 = ((ph & 1) + d->pad) & 1;
       const int Hp = (d->H - y0 + 1) >> 1, Wp = (d->W - x0 + 1) >> 1;
-      const long long rows = (long long)d->B * Hp * Wp;
-      p.ph_tiles[ph] = (int)((rows + 127) / 128);
-      if (p.ph_tiles[ph] > tmax) tmax = p.ph_tiles[ph];
+      p.ph_tiles[ph] = pl.ph_tiles[ph];
       p.fd_hw[ph] = nbm_fastdiv_make((unsigned)(Hp * Wp));     // (an empty class: no tile of it gets past its early exit)
       p.fd_w[ph] = nbm_fastdiv_make((unsigned)Wp);
     }
-    p.m_tiles = 4 * tmax;
   }
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
   hipStream_t st = (hipStream_t)stream;
-  // short K (<= 8 steps of 32) and a 16-byte epilogue: the three-workgroups-per-CU variant (see the template comment).
-  // Stride 2 (phased): a tile's K loop visits its parity class's taps only -- (N / 32) x {1, 2, 2, 4} steps for a 3x3; up to 16 steps
-  // (the largest class's step count decides: 128 -> 128 @94x256, steps 4 / 8 / 8 / 16: 3.61 -> 3.46 ms at B = 128 on the single-stage kernel)
-  const int ph_max = ((d->N + BK - 1) / BK) * ((d->kh + 1) / 2) * ((d->kw + 1) / 2);
-  // the 64-wide tile spends half the MFMA cycles per K-step: its prologue / epilogue weigh double, and the third workgroup pays up to
-  // K = 576 (layer1's 3x3 64 -> 64 @94x256 at B = 128: 2.39 -> 2.15 ms, round 5): up to 20 steps there
-  const int shortk_lim = d->Cin <= 64 ? 20 : 8;
-  const bool shortk = p.vec_epi && (p.phased ? ph_max <= 16 : ((d->N + BK - 1) / BK) * d->kh * d->kw <= shortk_lim);
-  // deep K: the half-step form of the two-stage kernel (three workgroups per CU, same bits; NBM_NN_H16=0: the two-stage kernel).  Read per
-  // call: the parity test flips it inside one process.
-  const char* hs_env = getenv("NBM_NN_H16");
-  const bool hs = !(hs_env && hs_env[0] == '0') && p.vec_epi;
-  if (d->Cin > 64) {
-    p.n_tiles = (d->Cin + 127) / 128;
-    const dim3 grid(p.m_tiles * p.n_tiles, 1, d->groups);
-    if (shortk) hipLaunchKernelGGL((igemm_nn_kernel<128, 1>), grid, dim3(256), 0, st, p);
-    else if (hs) hipLaunchKernelGGL((igemm_nn_kernel<128, 2, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((igemm_nn_kernel<128, 2>), grid, dim3(256), 0, st, p);
-  } else {
-    p.n_tiles = 1;
-    const dim3 grid(p.m_tiles, 1, d->groups);
-    if (shortk) hipLaunchKernelGGL((igemm_nn_kernel<64, 1>), grid, dim3(256), 0, st, p);
-    else if (hs) hipLaunchKernelGGL((igemm_nn_kernel<64, 2, true>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((igemm_nn_kernel<64, 2>), grid, dim3(256), 0, st, p);
+  switch (pl.kernel) {
+    case K_NN_128_S1: hipLaunchKernelGGL((igemm_nn_kernel<128, 1>), grid, block, 0, st, p); break;
+    case K_NN_128_H16: hipLaunchKernelGGL((igemm_nn_kernel<128, 2, true>), grid, block, 0, st, p); break;
+    case K_NN_128: hipLaunchKernelGGL((igemm_nn_kernel<128, 2>), grid, block, 0, st, p); break;
+    case K_NN_64_S1: hipLaunchKernelGGL((igemm_nn_kernel<64, 1>), grid, block, 0, st, p); break;
+    case K_NN_64_H16: hipLaunchKernelGGL((igemm_nn_kernel<64, 2, true>), grid, block, 0, st, p); break;
+    case K_NN_64: hipLaunchKernelGGL((igemm_nn_kernel<64, 2>), grid, block, 0, st, p); break;
+    default: return NBM_EINVAL;
   }
   return nbm_launch_status();
 }
 
 extern "C" int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream) {
-  BwdParams p{};
-  int rc = fill_common(d, p);
-  if (rc) return rc;
-  if (!d->x) return NBM_EINVAL;
-  if ((d->g_ld & 3) || (d->g_gs & 3) || !nbm_aligned16(d->g) || d->g_ld < ((d->N + 3) / 4) * 4) return NBM_EALIGN;
-  p.b_generic = ((d->Cin & 3) || (d->x_ld & 3) || (d->x_gs & 3) || !nbm_aligned16(d->x)) ? 1 : 0;
-  const int taps = d->kh * d->kw;
-  if (d->out_ld < taps * d->Cin) return NBM_EINVAL;
-  // Plain GEMMs whose column count is 64 past a multiple of 128 (the cell-domain planes of the deferred lateral: [T][256]^T x [T][448]): the
-  // 128-wide tiles would multiply 64 columns of padding in the last tile (1 / 8 of the MFMA work of 448 columns: 110 against 122 TF/s for
-  // the 384-column twin, round 5) -- the first Cin - 64 columns on 128-wide tiles, the last 64 on the 64-wide kernel.  Same sums per element
-  // (the split over the pixels is chosen per launch; the atomics make the order free anyway).
-  if (taps == 1 && d->stride == 1 && d->pad == 0 && !p.b_generic && d->Cin > 128 && (d->Cin & 127) == 64) {
+  if (!d) return NBM_EINVAL;
+  const GemmPlan pl = plan_wgrad(*d, read_gemm_switches(2));
+  if (pl.rc) return pl.rc;
+  if (pl.halves) {               // Cin is 64 past a multiple of 128: the first Cin - 64 columns, then the last 64 (see plan_wgrad)
     nbm_bwd_desc a = *d, b = *d;
     a.Cin = d->Cin - 64;
     b.Cin = 64;
     b.x = d->x + (d->Cin - 64);
     b.out = d->out + (d->Cin - 64);
     b.bias_grad = nullptr;                                   // (the column sums of G come from the first launch)
-    rc = nbm_conv_wgrad(&a, stream);
+    const int rc = nbm_conv_wgrad(&a, stream);
     return rc ? rc : nbm_conv_wgrad(&b, stream);
   }
-  p.M = d->B * d->Ho * d->Wo;
-  const bool narrow_m = d->N <= 64 && !p.b_generic;            // 64-row dW tiles: no MFMA spent on the zero half of a 128-row G tile
-  p.m_tiles = narrow_m ? 1 : (d->N + 127) / 128;
+  const int M = d->B * d->Ho * d->Wo;
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]), block(pl.block);
   hipStream_t st = (hipStream_t)stream;
-  const bool wide = !p.b_generic && d->Cin > 64;
-  const int BN = wide ? 128 : 64;
-  p.n_tiles = p.b_generic ? (taps * d->Cin + BN - 1) / BN : taps * ((d->Cin + BN - 1) / BN);
-  // Split the pixel reduction so that the grid fills the chip in WHOLE rounds: 512 workgroups are resident at once
-  // (256 CUs x 2), all of equal length, so a grid of 4.01 rounds costs 5 (the old ">= 2048 workgroups" rule hit exactly
-  // that on the largest layer: 54 tiles x 38 splits = 2052).  Pick the split count with the best fill of its last
-  // round among those with >= 8 K-steps per split and <= 16 rounds; ties go to fewer splits (fewer atomics).
-  const int tiles = p.m_tiles * p.n_tiles * d->groups;
-  const int max_splits = (p.M + 8 * BK - 1) / (8 * BK);
-  // (512 = 256 CUs x the two workgroups of the 128 x 128 instantiation.  The narrower instantiations hold 3 or 4 per CU; sizing the rounds
-  // for 768 / 1024 was measured in round 5 and changes nothing -- 2.161 vs 2.155 ms on layer1's 3x3: a CU with fewer workgroups left runs
-  // them faster, the matrix pipe is what they share -- scripts/wgrad_cycles.py, in the git history)
-  const int slots = 512;
-  int splits = 1;
-  double best = -1.0;
-  for (int sp = 1; sp <= max_splits && (long long)sp * tiles <= 16ll * slots; ++sp) {
-    const long long wg = (long long)sp * tiles;
-    const long long rounds = (wg + slots - 1) / slots;
-    const double fill = (double)wg / (double)(rounds * slots);
-    if (fill > best + 0.005) { best = fill; splits = sp; }
+  if (pl.kernel >= K_SPLIT_TN_R0) {
+    SplitTnParams q{};
+    q.g = d->g; q.x = d->x; q.out = d->out; q.row_scale = d->row_scale;
+    q.g_gs = d->g_gs; q.x_gs = d->x_gs; q.out_gs = d->out_gs;
+    q.M = M; q.N = d->N; q.K = d->Cin; q.g_ld = d->g_ld; q.x_ld = d->x_ld; q.out_ld = d->out_ld; q.alpha = d->alpha;
+    q.n_tiles = pl.n_tiles;
+    q.k_chunk = pl.k_chunk;
+    return split_tn_launch(q, pl, st);
   }
-  p.plain = (d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0) ? 1 : 0;
-  // opt-in (NBM_SPLIT_BF16=1): plain weight-gradient GEMMs (1x1 convolutions, nn.Linear, the grouped Winograd- / cell-domain
-  // products) with >= 192 rows and > 64 columns on the bf16 matrix pipe through split fp32 operands (igemm_split_tn.hip).  Read per call;
-  // chosen by the LAYER, never by the number of pixels.  The bias gradient is not produced there (the caller sums the columns of G).
-  {
-    const char* se = getenv("NBM_SPLIT_BF16");
-    const char* te = getenv("NBM_SPLIT_TN");
-    if (se && se[0] == '1' && !(te && te[0] == '0') && p.plain && !p.b_generic && !d->bias_grad && d->N >= 192 && d->Cin > 64 &&
-        (d->out_ld >= d->Cin) && (long long)32 * d->g_ld * 4 < 0x40000000ll && (long long)32 * d->x_ld * 4 < 0x40000000ll) {
-      nbm_igemm::SplitTnParams q{};
-      q.g = d->g; q.x = d->x; q.out = d->out; q.row_scale = d->row_scale;
-      q.g_gs = d->g_gs; q.x_gs = d->x_gs; q.out_gs = d->out_gs;
-      q.M = p.M; q.N = d->N; q.K = d->Cin; q.g_ld = d->g_ld; q.x_ld = d->x_ld; q.out_ld = d->out_ld; q.alpha = d->alpha;
-      q.n_tiles = (d->Cin + 127) / 128;
-      const int tiles_s = ((d->N + 255) / 256) * q.n_tiles * d->groups;
-      const int slots_s = 256;                                       // one workgroup per CU
-      const int max_sp = (p.M + 16 * 32 - 1) / (16 * 32);            // >= 32 K16 stages per split
-      int sp_best = 1;
-      double fill_best = -1.0;
-      for (int sp = 1; sp <= max_sp && (long long)sp * tiles_s <= 16ll * slots_s; ++sp) {
-        const long long wgs = (long long)sp * tiles_s;
-        const long long rounds = (wgs + slots_s - 1) / slots_s;
-        const double fill = (double)wgs / (double)(rounds * slots_s);
-        if (fill > fill_best + 0.005) { fill_best = fill; sp_best = sp; }
-      }
-      q.k_chunk = (((p.M + sp_best - 1) / sp_best) + 31) / 32 * 32;
-      const int sp_n = (p.M + q.k_chunk - 1) / q.k_chunk;
-      return nbm_igemm::split_tn_launch(q, sp_n, d->groups, st);
-    }
+  BwdParams p = fill_common(d, pl);
+  p.M = M;
+  p.b_generic = pl.b_generic;
+  p.plain = pl.plain;
+  p.k_chunk = pl.k_chunk;
+  switch (pl.kernel) {
+    case K_TN_GENERIC: hipLaunchKernelGGL((igemm_tn_kernel<64, B_GENERIC>), grid, block, 0, st, p); break;
+    case K_TN_128_SAME_M64: hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 64>), grid, block, 0, st, p); break;
+    case K_TN_128_STRIDED_M64: hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED, 64>), grid, block, 0, st, p); break;
+    case K_TN_64_SAME_M64: hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME, 64>), grid, block, 0, st, p); break;
+    case K_TN_64_STRIDED_M64: hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED, 64>), grid, block, 0, st, p); break;
+    case K_TN_128_SAME: hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME>), grid, block, 0, st, p); break;
+    case K_TN_128_STRIDED: hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED>), grid, block, 0, st, p); break;
+    case K_TN_64_SAME: hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME>), grid, block, 0, st, p); break;
+    case K_TN_64_STRIDED: hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED>), grid, block, 0, st, p); break;
+    default: return NBM_EINVAL;
   }
-  p.k_chunk = (((p.M + splits - 1) / splits) + BK - 1) / BK * BK;
-  splits = (p.M + p.k_chunk - 1) / p.k_chunk;
-  dim3 grid(p.m_tiles * p.n_tiles, splits, d->groups);
-  const bool same = !p.b_generic && d->stride == 1 && d->Ho == d->H && d->Wo == d->W && (d->Wo >= BK || p.plain) &&
-                    (long long)BK * d->x_ld * 4 < 0x40000000ll;
-  if (p.b_generic) hipLaunchKernelGGL((igemm_tn_kernel<64, B_GENERIC>), grid, dim3(256), 0, st, p);
-  else if (narrow_m) {
-    if (wide && same) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 64>), grid, dim3(256), 0, st, p);
-    else if (wide) hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED, 64>), grid, dim3(256), 0, st, p);
-    else if (same) hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME, 64>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED, 64>), grid, dim3(256), 0, st, p);
-  }
-  else if (wide && same) hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME>), grid, dim3(256), 0, st, p);
-  else if (wide) hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED>), grid, dim3(256), 0, st, p);
-  else if (same) hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME>), grid, dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED>), grid, dim3(256), 0, st, p);
   return nbm_launch_status();
 }

@@ -182,11 +182,7 @@ __global__ __launch_bounds__(256, 3) void igemm_h16_kernel(const IgemmParams p) 
 
 }  // namespace
 
-int nbm_igemm::h16_launch(const IgemmParams& p0, int groups, hipStream_t st) {
-  IgemmParams p = p0;
-  p.m_tiles = (p.M + BM - 1) / BM;
-  p.n_tiles = (p.N + BN - 1) / BN;
-  const dim3 grid(p.m_tiles * p.n_tiles, 1, groups);
-  hipLaunchKernelGGL(igemm_h16_kernel, grid, dim3(256), 0, st, p);
+int nbm_igemm::h16_launch(const IgemmParams& p, const GemmPlan& pl, hipStream_t st) {
+  hipLaunchKernelGGL(igemm_h16_kernel, dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(256), 0, st, p);
   return nbm_launch_status();
 }

@@ -2,6 +2,7 @@
 // fp32 operands).  Internal to the library -- the C ABI is nbm_gemm_desc (include/nbm_hip.h).
 #pragma once
 #include "nbm_common.h"
+#include "igemm_plan.h"
 
 namespace nbm_igemm {
 
@@ -35,11 +36,12 @@ struct IgemmParams {
   nbm_fastdiv fd_howo, fd_wo, fd_rows_thw, fd_rows_tw;
 };
 
-// igemm_split.hip: 256 x 128 tiles on the bf16 matrix pipe (fast gather, 16-byte epilogue, N > 64, nk > 8 only; the caller checks)
-int split_launch(const IgemmParams& p, int groups, hipStream_t st);
+// igemm_split.hip: 256 x 128 tiles on the bf16 matrix pipe (fast gather, 16-byte epilogue, N > 64, nk > 8 only: plan_fwd's K_FWD_SPLIT_R*,
+// the remainder form of its K pipeline)
+int split_launch(const IgemmParams& p, const GemmPlan& pl, hipStream_t st);
 
 // igemm_h16.hip: the 128 x 128 tile with half-step LDS stages, three workgroups per CU (fast gather, 16-byte epilogue, N > 64; same bits as
 // igemm_kernel<128,128,...>)
-int h16_launch(const IgemmParams& p, int groups, hipStream_t st);
+int h16_launch(const IgemmParams& p, const GemmPlan& pl, hipStream_t st);
 
 }  // namespace nbm_igemm

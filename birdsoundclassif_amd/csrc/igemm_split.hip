@@ -277,14 +277,11 @@ __global__ __launch_bounds__(256, 1) void igemm_split_kernel(const IgemmParams p
 
 }  // namespace
 
-int nbm_igemm::split_launch(const IgemmParams& p0, int groups, hipStream_t st) {
-  IgemmParams p = p0;
-  p.m_tiles = (p.M + BM - 1) / BM;
-  p.n_tiles = (p.N + BN - 1) / BN;
-  const dim3 grid(p.m_tiles * p.n_tiles, 1, groups);
-  switch ((2 * p.nk) % 6) {
-    case 0: hipLaunchKernelGGL((igemm_split_kernel<0>), grid, dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((igemm_split_kernel<2>), grid, dim3(256), 0, st, p); break;
+int nbm_igemm::split_launch(const IgemmParams& p, const GemmPlan& pl, hipStream_t st) {
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+  switch (pl.kernel) {
+    case K_FWD_SPLIT_R0: hipLaunchKernelGGL((igemm_split_kernel<0>), grid, dim3(256), 0, st, p); break;
+    case K_FWD_SPLIT_R2: hipLaunchKernelGGL((igemm_split_kernel<2>), grid, dim3(256), 0, st, p); break;
     default: hipLaunchKernelGGL((igemm_split_kernel<4>), grid, dim3(256), 0, st, p); break;
   }
   return nbm_launch_status();

@@ -1,6 +1,7 @@
 // Launch parameters of the split-bf16 weight-gradient kernel (igemm_split_tn.hip).  Internal to the library -- the C ABI is nbm_bwd_desc.
 #pragma once
 #include "nbm_common.h"
+#include "igemm_plan.h"
 
 namespace nbm_igemm {
 
@@ -14,7 +15,7 @@ struct SplitTnParams {
   float alpha;
 };
 
-// 256 x 128 tiles, one workgroup per CU; grid = (m_tiles * n_tiles, splits, groups)
-int split_tn_launch(const SplitTnParams& p, int splits, int groups, hipStream_t st);
+// 256 x 128 tiles, one workgroup per CU; grid = (m_tiles * n_tiles, splits, groups) and the remainder form as plan_wgrad chose them
+int split_tn_launch(const SplitTnParams& p, const GemmPlan& pl, hipStream_t st);
 
 }  // namespace nbm_igemm

@@ -260,11 +260,11 @@ __global__ __launch_bounds__(256, 1) void igemm_split_tn_kernel(const SplitTnPar
 
 }  // namespace
 
-int nbm_igemm::split_tn_launch(const SplitTnParams& p, int splits, int groups, hipStream_t st) {
-  const dim3 grid(((p.N + BM - 1) / BM) * p.n_tiles, splits, groups);
-  switch ((p.k_chunk >> 4) % 6) {
-    case 0: hipLaunchKernelGGL((igemm_split_tn_kernel<0>), grid, dim3(256), 0, st, p); break;
-    case 2: hipLaunchKernelGGL((igemm_split_tn_kernel<2>), grid, dim3(256), 0, st, p); break;
+int nbm_igemm::split_tn_launch(const SplitTnParams& p, const GemmPlan& pl, hipStream_t st) {
+  const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
+  switch (pl.kernel) {
+    case K_SPLIT_TN_R0: hipLaunchKernelGGL((igemm_split_tn_kernel<0>), grid, dim3(256), 0, st, p); break;
+    case K_SPLIT_TN_R2: hipLaunchKernelGGL((igemm_split_tn_kernel<2>), grid, dim3(256), 0, st, p); break;
     default: hipLaunchKernelGGL((igemm_split_tn_kernel<4>), grid, dim3(256), 0, st, p); break;
   }
   return nbm_launch_status();

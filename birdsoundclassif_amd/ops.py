@@ -4,6 +4,7 @@ streams); all arithmetic happens in the hand-written kernels.  Activations are N
 
 Every function raises if the tensor is not a contiguous float32 CUDA tensor -- there is no CPU path.
 """
+import collections
 import ctypes as C
 import os
 import math
@@ -1010,10 +1011,18 @@ def _bwd_desc(g, *, B, H, W, Cin, N, kh, kw, stride, pad, g_ld, groups=1, alpha=
     return d
 
 
-def split_tn():
-    """Plain weight-gradient GEMMs through the split-bf16 kernel (opt-in with NBM_SPLIT_BF16=1; NBM_SPLIT_TN=0 keeps them on the fp32
-    kernel).  The C side (nbm_conv_wgrad) applies the same switch and the same shape rule."""
-    return os.environ.get('NBM_SPLIT_BF16') == '1' and os.environ.get('NBM_SPLIT_TN', '1') != '0'
+GemmPlan = collections.namedtuple('GemmPlan', 'rc kernel grid block m_tiles n_tiles vec_epi fast slices phased ph_tiles splits k_chunk '
+                                              'plain b_generic narrow_m halves')
+
+
+def gemm_plan(kind, desc):
+    """What nbm_gemm_conv (kind 0, a GemmDesc), nbm_conv_dgrad (1) or nbm_conv_wgrad (2, a BwdDesc) would do with `desc` under the current
+    environment switches: the kernel instantiation by name, its grid and the tiling values (nbm_gemm_plan, include/nbm_hip.h).  Nothing is
+    launched; works without a GPU.  rc != 0: the entry point's NBM_E* code, the other fields are unset."""
+    p = _lib.GemmPlan()
+    lib().nbm_gemm_plan(int(kind), C.byref(desc), C.byref(p))
+    return GemmPlan(p.rc, (p.name or b'').decode(), tuple(p.grid), p.block, p.m_tiles, p.n_tiles, p.vec_epi, p.fast, p.slices, p.phased,
+                    tuple(p.ph_tiles), p.splits, p.k_chunk, p.plain, p.b_generic, p.narrow_m, p.halves)
 
 
 def split_nn():
@@ -1071,11 +1080,6 @@ def conv_dgrad(g, w, out, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, g_ld=
 def conv_wgrad(g, x, out, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, g_ld=None, x_ld=None, out_ld=None,
                row_scale=None, alpha=1.0, groups=1, g_gs=0, x_gs=0, out_gs=0, bias_grad=None):
     """Raw nbm_conv_wgrad: out[N][kh*kw*Cin] += g^T x im2col(x); `out` must be zeroed (or hold a partial sum)."""
-    deferred_bias = None
-    if (bias_grad is not None and groups == 1 and kh == 1 and kw == 1 and stride == 1 and pad == 0 and N >= 192 and Cin > 64 and
-            Cin % 4 == 0 and split_tn()):
-        # the split-bf16 weight-gradient kernel (opt-in) does not sum the columns of G: the bias gradient comes from nbm_colsum
-        deferred_bias, bias_grad = bias_grad, None
     d = _bwd_desc(g, B=B, H=H, W=W, Cin=Cin, N=N, kh=kh, kw=kw, stride=stride, pad=pad,
                   g_ld=N if g_ld is None else g_ld, groups=groups, alpha=alpha)
     d.x, d.out = x.data_ptr(), out.data_ptr()
@@ -1083,6 +1087,12 @@ def conv_wgrad(g, x, out, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, g_ld=
     d.out_ld = kh * kw * Cin if out_ld is None else out_ld
     d.row_scale = row_scale.data_ptr() if row_scale is not None else None
     d.g_gs, d.x_gs, d.out_gs = g_gs, x_gs, out_gs
+    deferred_bias = None
+    if bias_grad is not None and groups == 1:
+        # the split-bf16 weight-gradient kernel (opt-in) does not sum the columns of G: where the library takes it for this launch without
+        # a bias gradient, the bias gradient comes from nbm_colsum (one group's sums) instead of riding along
+        if gemm_plan(2, d).kernel.startswith('igemm_split_tn_kernel'):
+            deferred_bias, bias_grad = bias_grad, None
     d.bias_grad = bias_grad.data_ptr() if bias_grad is not None else None       # [N] zeros: += column sums of g
     if FLOPS is not None:
         FLOPS[0] += 2.0 * B * d.Ho * d.Wo * N * kh * kw * Cin * groups

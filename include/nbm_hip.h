@@ -560,6 +560,30 @@ int nbm_conv_dgrad(const nbm_bwd_desc* d, void* stream);
  * Also the plain C[N][Cin] += A[M][N]^T * B[M][Cin] ("TN") GEMM. */
 int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream);
 
+/* The launch plan of the three GEMM entry points: which kernel instantiation a descriptor runs on, with what grid, and the tiling values
+ * the launch derives beyond the descriptor (csrc/igemm_plan.h; no counterpart in the reference, whose convolutions are dispatched inside
+ * torch).  nbm_gemm_plan reads the environment switches as the entry point would, plans and launches NOTHING: it touches no HIP API and
+ * works on a machine without a GPU.  kind: 0 = nbm_gemm_conv (desc: nbm_gemm_desc), 1 = nbm_conv_dgrad, 2 = nbm_conv_wgrad (desc:
+ * nbm_bwd_desc).  Returns (and stores in rc) what the entry point would return before launching: NBM_OK or its NBM_E* code; on an error
+ * the other fields are unset.  halves = 1: the channel count is 64 past a multiple of 128 (N of nbm_gemm_conv, Cin of nbm_conv_wgrad) and
+ * the entry point runs the first count - 64 channels and the last 64 as two calls of itself; the plan is that of the first call. */
+typedef struct nbm_gemm_plan_t {
+  const char* name;      /* the kernel instantiation, e.g. "igemm_kernel<128,128,64,64,0,0,2,false>" (static storage)           */
+  int rc;
+  int kernel;            /* id of `name` (csrc/igemm_plan.h: GemmKernel)                                                        */
+  int grid[3], block;
+  int m_tiles, n_tiles;  /* tile counts as the kernel receives them                                                             */
+  int vec_epi;           /* 16-byte epilogue                                                                                    */
+  int fast;              /* forward: 16-byte gather (Cin % 32 == 0, aligned) instead of the generic one                         */
+  int slices;            /* stream1x1 forms: slices of N (grid y)                                                               */
+  int phased;            /* data gradient, stride 2: M tiles grouped by parity class, ph_tiles[class] tiles each                */
+  int ph_tiles[4];
+  int splits, k_chunk;   /* weight gradient: splits of the pixel reduction (grid y), pixels per split                           */
+  int plain, b_generic, narrow_m; /* weight gradient: 1x1 / stride 1 / pad 0; scalar gather of x; 64-row dW tiles               */
+  int halves;
+} nbm_gemm_plan_t;
+int nbm_gemm_plan(int kind, const void* desc, nbm_gemm_plan_t* out);
+
 int nbm_relu_bwd(const float* gy, const float* y, float* out, int64_t n, void* stream);
 int nbm_silu_bwd(const float* gy, const float* x, float* out, int64_t n, void* stream);
 /* out[i] = alpha*a[i] + beta*b[i % b_period] (b may be NULL; b_period 0: b has n elements): gradient accumulation, the
