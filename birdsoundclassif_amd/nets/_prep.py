@@ -65,6 +65,26 @@ def krsc(weight):
     return _cached(weight, 'krsc', make)
 
 
+def gconv(weight, groups):
+    """Grouped 3x3 weights [C, Cg, 3, 3] (checkpoint layout, C = groups * Cg) -> the fragment order of `nbm_gconv3x3`
+    (include/nbm_hip.h): [C / 16][9][CI / 16][64][4] with CI = max(Cg, 16), element (t, 3 r + s, j, lane, e) = W[n][ci - g(n) Cg][r][s]
+    for n = 16 t + (lane & 15) and the input channel ci = (16 t // CI) CI + 16 j + 4 (lane >> 4) + e when ci lies in n's group g(n),
+    else 0 -- groups narrower than 16 channels share a 16 x 16 fragment as a block diagonal."""
+    def make():
+        C, Cg, kh, kw = weight.shape
+        if (kh, kw) != (3, 3) or C != groups * Cg or 16 % min(Cg, 16) or Cg % 16 not in (0, Cg) or C % 16:
+            raise ValueError(f'gconv: no fragment layout for a {tuple(weight.shape)} weight in {groups} groups')
+        w = weight.detach().reshape(C, Cg, 9)
+        CI = max(Cg, 16)
+        if Cg < 16:
+            # row n of the 16-channel slab that holds its group: columns ci with ci // Cg == (n % 16) // Cg carry W[n][ci % Cg]
+            same = (torch.arange(16, device=w.device)[None, :] // Cg) == ((torch.arange(C, device=w.device) % 16) // Cg)[:, None]
+            w = w.repeat(1, 16 // Cg, 1) * same[:, :, None].to(w.dtype)
+        # [C, CI, 9] -> (t, n % 16, j, q, e, tap) -> (t, tap, j, q, n % 16, e)
+        return w.reshape(C // 16, 16, CI // 16, 4, 4, 9).permute(0, 5, 2, 3, 1, 4).reshape(C // 16, 9, CI // 16, 64, 4).contiguous()
+    return _cached(weight, ('gconv', int(groups)), make)
+
+
 def wino23(weight, transposed=False, m=2, scale=None):
     """Winograd F(m x m, 3x3) weights U[(m+2)^2][N][C] = (G g G^T)[i][j] of a [Cout, Cin, 3, 3] convolution (`nbm_wino_weight`:
     float64 arithmetic on the device, rounded once).  `transposed`: the weights of the DATA-GRADIENT convolution (kernel

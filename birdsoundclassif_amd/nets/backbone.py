@@ -5,6 +5,8 @@ Same classes / constructor arguments / state_dict keys as the reference: `backbo
 definition (public architecture, reference backbone.py:131 `getattr(torchvision.models, name)`) is
 stated here as parameter containers, and the forward is a chain of fp32-MFMA implicit-GEMM launches with
 FrozenBatchNorm affine + ReLU + residual fused into the epilogues.  Activations are NHWC.
+The ResNeXt names (resnext50_32x4d, resnext101_32x8d, resnext101_64x4d) are the same body with grouped bottlenecks, whose 3x3 runs
+on `ops.gconv3x3` (csrc/gconv.hip); they are forward-only.
 """
 import torch
 from torch import nn
@@ -15,6 +17,9 @@ from .position_encoding import build_position_encoding
 
 bcbk_channels = {'resnet': {'2': 64, '3': 256, '4': 512, '5': 1024, '6': 2048}}
 _RESNET_LAYERS = {'resnet50': [3, 4, 6, 3], 'resnet101': [3, 4, 23, 3], 'resnet152': [3, 8, 36, 3]}
+# ResNeXt (Xie et al. 2017; torchvision's names): name -> (layers, groups, base width); the taps keep the ResNet channel counts
+_RESNEXT = {'resnext50_32x4d': ([3, 4, 6, 3], 32, 4), 'resnext101_32x8d': ([3, 4, 23, 3], 32, 8),
+            'resnext101_64x4d': ([3, 4, 23, 3], 64, 4)}
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -78,12 +83,49 @@ class _Bottleneck(nn.Module):
         return Fn.conv(o, self.conv3.weight, scale=s, shift=b, residual=idt, act=ops.ACT_RELU)
 
 
+class _GroupedBottleneck(nn.Module):
+    """ResNeXt bottleneck (torchvision's `Bottleneck` with groups > 1; same module / state_dict names): 1x1 to `width` =
+    int(planes * base_width / 64) * groups channels, GROUPED 3x3 (stride on it) through `ops.gconv3x3` with bn2 + ReLU in its epilogue,
+    1x1 to 4 * planes with the shortcut in its epilogue.  Forward only: the grouped convolution has no backward kernels, so the
+    backbone has to be frozen to train what follows it."""
+
+    def __init__(self, inplanes, planes, stride, downsample, norm_layer, groups, base_width):
+        super().__init__()
+        width = int(planes * base_width / 64) * groups
+        self.conv1 = nn.Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = norm_layer(width)
+        self.conv2 = nn.Conv2d(width, width, 3, stride=stride, padding=1, groups=groups, bias=False)
+        self.bn2 = norm_layer(width)
+        self.conv3 = nn.Conv2d(width, planes * 4, 1, bias=False)
+        self.bn3 = norm_layer(planes * 4)
+        self.downsample = downsample
+        self.stride, self.groups = stride, groups
+        self.mask_input, self.mask_gy = False, True           # (set by _ResNetBody; only Fn.Bottleneck reads them)
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('the grouped 3x3 convolution of a ResNeXt block has no backward pass: train with --lr_backbone 0 '
+                                      '(a frozen backbone), or run it under torch.no_grad()')
+        s, b = self.bn1.affine()
+        o = Fn.conv(x, self.conv1.weight, scale=s, shift=b, act=ops.ACT_RELU)
+        s, b = self.bn2.affine()
+        o = ops.gconv3x3(o, _prep.gconv(self.conv2.weight, self.groups), self.groups, stride=self.stride, scale=s, shift=b, relu=True)
+        if self.downsample is not None:
+            s, b = self.downsample[1].affine()
+            idt = Fn.conv(x, self.downsample[0].weight, scale=s, shift=b, stride=self.stride)
+        else:
+            idt = x
+        s, b = self.bn3.affine()
+        return Fn.conv(o, self.conv3.weight, scale=s, shift=b, residual=idt, act=ops.ACT_RELU)
+
+
 class _ResNetBody(nn.Module):
     """conv1/bn1/relu/maxpool/layer1..4 with torchvision's names; returns the 5 taps the reference takes
     with IntermediateLayerGetter (backbone.py:82-85): relu, layer1..layer4."""
 
-    def __init__(self, layers, norm_layer, dilation=False):
-        """`dilation` (reference backbone.py:129-131: torchvision's `replace_stride_with_dilation=[False, False, True]`): layer4 keeps
+    def __init__(self, layers, norm_layer, dilation=False, groups=1, base_width=64):
+        """`groups` > 1: ResNeXt blocks (`_GroupedBottleneck`) of `base_width` channels per group at layer1.
+        `dilation` (reference backbone.py:129-131: torchvision's `replace_stride_with_dilation=[False, False, True]`): layer4 keeps
         layer3's resolution -- its first block runs with stride 1 (3x3 dilation 1, like torchvision: the first block uses the
         PREVIOUS dilation), the following blocks with 3x3 / dilation 2 / padding 2.  Same parameters, same state_dict."""
         super().__init__()
@@ -98,7 +140,8 @@ class _ResNetBody(nn.Module):
                 ds = None
                 if bi == 0 and (st != 1 or inplanes != planes * 4):
                     ds = nn.Sequential(nn.Conv2d(inplanes, planes * 4, 1, stride=st, bias=False), norm_layer(planes * 4))
-                blocks.append(_Bottleneck(inplanes, planes, st, ds, norm_layer))
+                blocks.append(_Bottleneck(inplanes, planes, st, ds, norm_layer) if groups == 1 else
+                              _GroupedBottleneck(inplanes, planes, st, ds, norm_layer, groups, base_width))
                 if dilation and li == 4 and bi > 0:                   # state_dict / repr parity with torchvision's module
                     blocks[-1].conv2.dilation, blocks[-1].conv2.padding = (2, 2), (2, 2)
                 blocks[-1].mask_input = not (li == 1 and bi == 0)      # layer1.0 reads the max-pool output
@@ -155,11 +198,16 @@ class Backbone(BackboneBase):
     """ResNet backbone with frozen BatchNorm (reference backbone.py:116-132)."""
 
     def __init__(self, name, in_channels, train_backbone, dilation, norm_layer_name):
-        if name not in _RESNET_LAYERS:
-            raise ValueError(f'not supported {name}: the accelerated path implements {sorted(_RESNET_LAYERS)}')
+        if name not in _RESNET_LAYERS and name not in _RESNEXT:
+            raise ValueError(f'not supported {name}: the accelerated path implements {sorted(_RESNET_LAYERS) + sorted(_RESNEXT)}')
         if norm_layer_name != 'frozen_batchnorm':
             raise NotImplementedError('only --norm_layer_backbone frozen_batchnorm (reference default) is implemented')
-        super().__init__(_ResNetBody(_RESNET_LAYERS[name], FrozenBatchNorm2d, dilation=dilation), name, in_channels, train_backbone)
+        layers, groups, base_width = _RESNEXT[name] if name in _RESNEXT else (_RESNET_LAYERS[name], 1, 64)
+        super().__init__(_ResNetBody(layers, FrozenBatchNorm2d, dilation=dilation, groups=groups, base_width=base_width), name,
+                         in_channels, train_backbone)
+        if groups > 1 and not train_backbone and hasattr(self, 'init_conv'):
+            # no gradient passes a grouped block, so none can reach init_conv; its learning rate is --lr_backbone = 0 anyway
+            self.init_conv.requires_grad_(False)
 
 
 class Joiner(nn.Sequential):

@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import GemmDesc, RoiDesc, check
+from ._lib import GconvDesc, GemmDesc, RoiDesc, check
 
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_LEAKY = 0, 1, 2, 3
 
@@ -145,6 +145,48 @@ def conv2d(x, w, kh=1, kw=1, stride=1, pad=0, scale=None, shift=None, residual=N
     gemm_conv(x, w, y, B=B, H=H, W=W, Cin=Cin, N=N, kh=kh, kw=kw, stride=stride, pad=pad, Ho=Ho, Wo=Wo,
               w_ld=w.shape[1] if w_ld is None else w_ld, scale=scale, shift=shift, residual=residual,
               alpha=alpha, act=act, up=up, bits_out=bits_out)
+    return y
+
+
+def gconv3x3(x, w_prepared, groups, stride=1, scale=None, shift=None, relu=False, out=None, kh=3, kw=3, pad=1):
+    """Grouped 3x3 / pad 1 convolution (+ per-channel scale / shift, ReLU) of an NHWC map.  `w_prepared` = `_prep.gconv(weight, groups)`,
+    [C / 16, 9, max(Cg, 16) / 16, 64, 4] with C = groups * Cg; x [B,H,W,x_ld >= C] (channels beyond C are pitch) -> [B,Ho,Wo,C], or into
+    `out` [B,Ho,Wo,y_ld >= C] (its channels beyond C are left alone).  What the kernel does not implement raises (kh, kw and pad are
+    only there to be refused): there is no slow path."""
+    _chk(x, name='x'), _chk(w_prepared, name='w_prepared')
+    if x.dim() != 4 or w_prepared.dim() != 5 or tuple(w_prepared.shape[1::2]) != (9, 64) or w_prepared.shape[4] != 4 or groups <= 0 \
+            or (16 * w_prepared.shape[0]) % groups:
+        raise ValueError('gconv3x3: x must be [B,H,W,C] and w_prepared the output of _prep.gconv for these groups')
+    B, H, W, x_ld = x.shape
+    n_ch = 16 * w_prepared.shape[0]
+    Cg = n_ch // groups
+    if max(Cg, 16) != 16 * w_prepared.shape[2]:
+        raise ValueError(f'gconv3x3: w_prepared {tuple(w_prepared.shape)} does not belong to {groups} groups of {Cg} channels')
+    Ho, Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    y = out if out is not None else torch.empty((B, Ho, Wo, n_ch), device=x.device, dtype=torch.float32)
+    _chk(y, name='out')
+    if y.dim() != 4 or tuple(y.shape[:3]) != (B, Ho, Wo) or y.shape[3] < n_ch or x_ld < n_ch:
+        raise ValueError(f'gconv3x3: out must be [{B},{Ho},{Wo},>={n_ch}] and x at least {n_ch} channels wide')
+    for v, nm in ((scale, 'scale'), (shift, 'shift')):
+        if v is not None and _chk(v, name=nm).numel() != n_ch:
+            raise ValueError(f'gconv3x3: {nm} must hold {n_ch} values')
+    d = GconvDesc()
+    d.x, d.w, d.y = x.data_ptr(), w_prepared.data_ptr(), y.data_ptr()
+    d.scale = scale.data_ptr() if scale is not None else None
+    d.shift = shift.data_ptr() if shift is not None else None
+    d.B, d.H, d.W, d.groups, d.Cg = B, H, W, groups, Cg
+    d.kh, d.kw, d.stride, d.pad, d.Ho, d.Wo = kh, kw, stride, pad, Ho, Wo
+    d.x_ld, d.y_ld, d.relu = x_ld, y.shape[3], int(bool(relu))
+    if FLOPS is not None:
+        FLOPS[0] += 2.0 * 9 * Cg * n_ch * B * Ho * Wo         # algorithmic: the block-diagonal zeros of Cg < 16 are not counted
+    if _prof_all():
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        check(lib().nbm_gconv3x3(C.byref(d), _stream()), 'nbm_gconv3x3')
+        ev1.record()
+        PROFILE.append(((Cg, n_ch, kh, H, W, B, groups, stride, 'gconv'), ev0, ev1))
+        return y
+    check(lib().nbm_gconv3x3(C.byref(d), _stream()), 'nbm_gconv3x3')
     return y
 
 

@@ -109,6 +109,35 @@ typedef struct nbm_gemm_desc {
  * summation order.  Default: the fp32 matrix instruction. */
 int nbm_gemm_conv(const nbm_gemm_desc* d, void* stream);
 
+/* Grouped 3x3 convolution on the fp32 matrix instruction v_mfma_f32_16x16x4_f32 (csrc/gconv.hip), NHWC fp32:
+ *
+ *   y[b][oy][ox][g*Cg + n] = relu?( scale[.] * sum_{r,s,c} x[b][oy*stride-1+r][ox*stride-1+s][g*Cg + c] * W[g*Cg + n][c][r][s] + shift[.] )
+ *
+ * 3x3, pad 1, dilation 1, stride 1 or 2, zeros outside the image; `groups` groups of Cg input = Cg output channels, Cg in
+ * {4, 8, 16, 32, 64}, C = groups * Cg a multiple of 64.  scale / shift [C] are optional (the folded FrozenBatchNorm2d).
+ * w is the PREPARED weight, C * 9 * max(Cg, 16) floats in the kernel's fragment order (`_prep.gconv` of the host layer):
+ *   w[t][tap = 3 r + s][j][lane][e] = W[n][ci][r][s]  when input channel ci and output channel n lie in the same group, else 0,
+ *   n = 16 t + (lane & 15), ci = (16 t / CI) * CI + 16 j + 4 (lane >> 4) + e, CI = max(Cg, 16), j < CI / 16, lane < 64, e < 4.
+ * Anything else -- another Cg, kernel size, padding or stride, C % 64 != 0, a pointer that is not 16-byte aligned or a pitch that is no
+ * multiple of 4 -- returns NBM_EUNSUPPORTED and launches nothing: there is no slow path.  Allocates nothing, clears nothing.
+ *
+ * Replaces: the grouped `conv2` (+ bn2 + ReLU) of torchvision's ResNeXt Bottleneck, which the reference reaches through
+ *   backbone.py:131 `getattr(torchvision.models, name)` with name = resnext50_32x4d / resnext101_32x8d / resnext101_64x4d. */
+typedef struct nbm_gconv_desc {
+  const float* x;      /* [B][H][W] pixels of x_ld floats, C valid channels    */
+  const float* w;      /* prepared weights, see above                          */
+  float* y;            /* [B][Ho][Wo] pixels of y_ld floats, C valid channels  */
+  const float* scale;  /* [C] or NULL                                          */
+  const float* shift;  /* [C] or NULL                                          */
+  int B, H, W;
+  int groups, Cg;
+  int kh, kw, stride, pad;
+  int Ho, Wo;          /* (H - 1) / stride + 1, (W - 1) / stride + 1           */
+  int x_ld, y_ld;
+  int relu;
+} nbm_gconv_desc;
+int nbm_gconv3x3(const nbm_gconv_desc* d, void* stream);
+
 /* Winograd transforms for 3x3 / stride 1 / pad 1 convolutions (the FPN output convolutions, fpn.py:137,145, and their data /
  * weight gradients).  m = 2: F(2x2,3x3), 16 transformed planes, used by the forward pass (error ~3e-6, proposals stay
  * bit-identical to the reference); m = 4: F(4x4,3x3) with interpolation points {0, 1, -1, 1/2, -2, inf}, 36 planes, used by
