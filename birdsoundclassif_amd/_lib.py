@@ -112,6 +112,10 @@ SIGNATURES = {
     'nbm_nan_images': [_P, _I, _L, _P, _P],
     'nbm_rpn_select': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     'nbm_nms_batched': [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P],
+    'nbm_rpn_select_big_workspace': [_I, _I, C.POINTER(C.c_int64)],
+    'nbm_rpn_select_big': [_P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P, _P, _P, _P, _P],
+    'nbm_nms_big_workspace': [_I, _I, C.POINTER(C.c_int64)],
+    'nbm_nms_big': [_P, _P, _P, _I, _I, _F, _I, _P, _L, _P, _P, _P, _P, _P],
     'nbm_roi_pool': [C.POINTER(RoiDesc), _P],
     'nbm_rcnn_post': [_P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P],
     # ---- per-file merge (run_detection.merge_images)

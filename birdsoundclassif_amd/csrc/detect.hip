@@ -85,6 +85,33 @@ __device__ __forceinline__ void seg_range(const int* __restrict__ seg, int B, in
 // composite key = (score_key << 32) | ~index : unique, descending order == (score desc, index asc)
 constexpr int SEL_THREADS = 1024;
 
+// The N-th largest composite key of an image, N = *s_need on entry (1 <= N <= KA), left in *s_prefix: 8 passes of 8 bits, MSB
+// first, each a histogram of the next byte over the keys that match the prefix found so far.  Whole workgroup; *s_prefix = 0
+// on entry, hist = 256 LDS counters.
+__device__ __forceinline__ void select_threshold(const uint32_t* __restrict__ kb, int KA, unsigned int* hist,
+                                                 unsigned long long* s_prefix, int* s_need) {
+  const int tid = threadIdx.x;
+  for (int pass = 7; pass >= 0; --pass) {
+    for (int i = tid; i < 256; i += SEL_THREADS) hist[i] = 0u;
+    __syncthreads();
+    const int shift = pass * 8;
+    const unsigned long long prefix = *s_prefix;
+    const unsigned long long himask = pass == 7 ? 0ull : (~0ull << (shift + 8));
+    for (int i = tid; i < KA; i += SEL_THREADS) {
+      const unsigned long long c = ((unsigned long long)kb[i] << 32) | (unsigned int)(~(unsigned int)i);
+      if ((c & himask) == prefix) atomicAdd(&hist[(c >> shift) & 255ull], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int need = *s_need, d = 255;
+      for (; d > 0; --d) { if ((int)hist[d] >= need) break; need -= (int)hist[d]; }
+      *s_need = need;
+      *s_prefix = prefix | ((unsigned long long)d << shift);
+    }
+    __syncthreads();
+  }
+}
+
 __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(
     const float* __restrict__ boxes, const uint32_t* __restrict__ keys, const int* __restrict__ keep_count, int B,
     int KA, int top_n, int fail_below, int cap, float* __restrict__ sel_boxes, float* __restrict__ sel_scores,
@@ -112,26 +139,7 @@ __global__ __launch_bounds__(SEL_THREADS) void rpn_select_kernel(
   const int N = s_N;
   for (int i = tid; i < cap; i += SEL_THREADS) buf[i] = 0ull;
   if (N > 0) {
-    // 8 passes of 8 bits, MSB first: find the N-th largest composite key
-    for (int pass = 7; pass >= 0; --pass) {
-      for (int i = tid; i < 256; i += SEL_THREADS) hist[i] = 0u;
-      __syncthreads();
-      const int shift = pass * 8;
-      const unsigned long long prefix = s_prefix;
-      const unsigned long long himask = pass == 7 ? 0ull : (~0ull << (shift + 8));
-      for (int i = tid; i < KA; i += SEL_THREADS) {
-        const unsigned long long c = ((unsigned long long)kb[i] << 32) | (unsigned int)(~(unsigned int)i);
-        if ((c & himask) == prefix) atomicAdd(&hist[(c >> shift) & 255ull], 1u);
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int need = s_need, d = 255;
-        for (; d > 0; --d) { if ((int)hist[d] >= need) break; need -= (int)hist[d]; }
-        s_need = need;
-        s_prefix = prefix | ((unsigned long long)d << shift);
-      }
-      __syncthreads();
-    }
+    select_threshold(kb, KA, hist, &s_prefix, &s_need);
     const unsigned long long thr = s_prefix;  // exactly N composites are >= thr
     for (int i = tid; i < KA; i += SEL_THREADS) {
       const unsigned long long c = ((unsigned long long)kb[i] << 32) | (unsigned int)(~(unsigned int)i);
@@ -244,6 +252,210 @@ __global__ void nms_gather_kernel(const float* __restrict__ boxes, const float* 
     }
   }
 }
+
+// ------------------------------------------------------------------ proposals beyond 4 096 boxes per image
+// nbm_rpn_select_big / nbm_nms_big: the same contracts as nbm_rpn_select / nbm_nms_batched for cap up to BIG_CAP_MAX, with
+// workspaces linear in B * cap (DESIGN "Proposals beyond 4 096").
+constexpr int BIG_CAP_MAX = 65536;
+constexpr int SORT_RUN = 4096;               // composite keys of one LDS-sorted run: 32 KiB
+
+// One step (k, j) of the descending bitonic network on the run[0, len) that starts at element `base` of the whole sequence:
+// a thread takes pairs (i, i + j), never an idle half.  Ends with a barrier.
+__device__ __forceinline__ void bitonic_step(unsigned long long* run, int len, int base, int k, int j) {
+  for (int t = threadIdx.x; t < (len >> 1); t += SEL_THREADS) {
+    const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+    const unsigned long long x = run[i], y = run[i + j];
+    const bool desc = ((base + i) & k) == 0;
+    if (desc ? (x < y) : (x > y)) { run[i] = y; run[i + j] = x; }
+  }
+  __syncthreads();
+}
+
+// One workgroup per image.  The radix search is rpn_select_kernel's; the N composites at or above the threshold go to the
+// image's slice of sort_ws, padded with zeros to P = the power of two at or above N, and are sorted there: runs of
+// min(P, SORT_RUN) keys in LDS, then for every longer stage k the steps j >= SORT_RUN in global memory and the steps below
+// it run by run in LDS again.  sort_ws is written and read by this workgroup alone, between barriers.
+__global__ __launch_bounds__(SEL_THREADS) void rpn_select_big_kernel(
+    const float* __restrict__ boxes, const uint32_t* __restrict__ keys, const int* __restrict__ keep_count, int B,
+    int KA, int top_n, int fail_below, int cap, unsigned long long* sort_ws, float* __restrict__ sel_boxes,
+    float* __restrict__ sel_scores, int* __restrict__ n_sel, const int* __restrict__ seg) {
+  __shared__ unsigned long long run[SORT_RUN];
+  __shared__ unsigned int hist[256];
+  __shared__ unsigned long long s_prefix;
+  __shared__ int s_need, s_count, s_N;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const uint32_t* kb = keys + (long long)b * KA;
+  unsigned long long* g = sort_ws + (long long)b * cap;
+
+  if (tid == 0) {
+    int lo, hi, mn = 0x7fffffff;
+    seg_range(seg, B, b, lo, hi);
+    for (int i = lo; i < hi; ++i) mn = min(mn, keep_count[i]);
+    int N = min(min(top_n, mn), KA);               // a count above KA cannot be met: the search needs N existing keys
+    if (N < fail_below || N < 0) N = 0;
+    s_N = N; s_need = N; s_prefix = 0ull; s_count = 0;
+    n_sel[b] = N;
+  }
+  __syncthreads();
+  const int N = s_N;
+  if (N > 0) {
+    int P = 64;
+    while (P < N) P <<= 1;                         // N <= top_n <= cap, a power of two: P <= cap
+    const int len = min(P, SORT_RUN);
+    select_threshold(kb, KA, hist, &s_prefix, &s_need);
+    const unsigned long long thr = s_prefix;       // exactly N composites are >= thr
+    for (int i = tid; i < KA; i += SEL_THREADS) {
+      const unsigned long long c = ((unsigned long long)kb[i] << 32) | (unsigned int)(~(unsigned int)i);
+      if (c >= thr) { const int pos = atomicAdd(&s_count, 1); if (pos < P) g[pos] = c; }
+    }
+    for (int i = N + tid; i < P; i += SEL_THREADS) g[i] = 0ull;
+    __syncthreads();
+    for (int base = 0; base < P; base += len) {
+      for (int i = tid; i < len; i += SEL_THREADS) run[i] = g[base + i];
+      __syncthreads();
+      for (int k = 2; k <= len; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) bitonic_step(run, len, base, k, j);
+      for (int i = tid; i < len; i += SEL_THREADS) g[base + i] = run[i];
+      __syncthreads();
+    }
+    for (int k = len << 1; k <= P; k <<= 1) {
+      for (int j = k >> 1; j >= len; j >>= 1) {
+        for (int t = tid; t < (P >> 1); t += SEL_THREADS) {
+          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+          const unsigned long long x = g[i], y = g[i + j];
+          const bool desc = (i & k) == 0;
+          if (desc ? (x < y) : (x > y)) { g[i] = y; g[i + j] = x; }
+        }
+        __syncthreads();
+      }
+      for (int base = 0; base < P; base += len) {
+        for (int i = tid; i < len; i += SEL_THREADS) run[i] = g[base + i];
+        __syncthreads();
+        for (int j = len >> 1; j > 0; j >>= 1) bitonic_step(run, len, base, k, j);
+        for (int i = tid; i < len; i += SEL_THREADS) g[base + i] = run[i];
+        __syncthreads();
+      }
+    }
+  }
+  for (int r = tid; r < cap; r += SEL_THREADS) {
+    float* ob = sel_boxes + ((long long)b * cap + r) * 4;
+    if (r < N) {
+      const unsigned long long c = g[r];
+      const int idx = (int)(~(unsigned int)(c & 0xffffffffull));
+      const float* ib = boxes + ((long long)b * KA + idx) * 4;
+      ob[0] = ib[0]; ob[1] = ib[1]; ob[2] = ib[2]; ob[3] = ib[3];
+      sel_scores[(long long)b * cap + r] = nbm_key2f((uint32_t)(c >> 32));
+    } else {
+      ob[0] = ob[1] = ob[2] = ob[3] = 0.f;
+      sel_scores[(long long)b * cap + r] = 0.f;
+    }
+  }
+}
+
+constexpr int NMSB_THREADS = 1024, NMSB_WAVES = NMSB_THREADS / 64;
+constexpr int NMSB_KEPT_LDS = 2048;          // kept boxes held in LDS (32 KiB); later ones are read back from `rois`
+
+__device__ __forceinline__ unsigned long long readlane64(unsigned long long v, int k) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, k);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), k);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// The greedy walk of one image in one workgroup, 64 boxes per step, without a mask: lane l of every wave holds box
+// blk * 64 + l; wave w tests it against the kept boxes w, w + 16, ... found so far and against columns 4 w .. 4 w + 3 of
+// the block's own 64 x 64 tile; wave 0 then ORs the 16 verdicts and resolves the tile in registers (64 dependent bit steps on
+// the scalar unit, as merge.hip's scan).  A kept box goes straight to its output row, and to LDS while it fits: the walk
+// stops at post_n kept boxes (a survivor count enters the result only through min(post_n, .)), so every kept box that a
+// later step needs is an output row of this image.  `rois` is read back by the workgroup that wrote it, after a barrier.
+__global__ __launch_bounds__(NMSB_THREADS) void nms_big_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
+                                                               const int* __restrict__ n_in, int cap, float thresh, int post_n,
+                                                               float* rois, float* __restrict__ roi_scores,
+                                                               int* __restrict__ keep_cnt) {
+  __shared__ float kept[NMSB_KEPT_LDS][4];
+  __shared__ unsigned long long sup_sh[NMSB_WAVES];
+  __shared__ unsigned int diag_sh[NMSB_WAVES][64];
+  __shared__ unsigned long long kp_sh;
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = min(max(n_in[b], 0), cap);
+  const float* bb = boxes + (long long)b * cap * 4;
+  float* out = rois + (long long)b * post_n * 4;
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  int cnt = 0;
+  for (int blk = 0; blk * 64 < n && cnt < post_n; ++blk) {
+    const int i = blk * 64 + lane;
+    float me[4] = {0.f, 0.f, 0.f, 0.f};
+    if (i < n) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) me[e] = bb[(long long)i * 4 + e];
+    }
+    bool sup = false;
+    const int c_lds = min(cnt, NMSB_KEPT_LDS);
+    for (int k = wave; k < c_lds; k += NMSB_WAVES) sup |= iou_incl(kept[k], me) >= thresh;
+    for (int k = NMSB_KEPT_LDS + wave; k < cnt; k += NMSB_WAVES) sup |= iou_incl(out + (long long)k * 4, me) >= thresh;
+    const unsigned long long sm = __ballot(sup);
+    if (lane == 0) sup_sh[wave] = sm;
+    unsigned int d = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int jj = wave * 4 + q, j = blk * 64 + jj;
+      if (jj > lane && j < n && iou_incl(me, bb + (long long)j * 4) >= thresh) d |= 1u << q;
+    }
+    diag_sh[wave][lane] = d;
+    __syncthreads();
+    if (wave == 0) {
+      unsigned long long rem = 0ull, diag = 0ull;
+#pragma unroll
+      for (int w = 0; w < NMSB_WAVES; ++w) {
+        rem |= sup_sh[w];
+        diag |= (unsigned long long)diag_sh[w][lane] << (4 * w);
+      }
+      rem = readlane64(rem, 0);
+      const int m = min(64, n - blk * 64);
+      if (m < 64) rem |= ~0ull << m;
+#pragma unroll
+      for (int k = 0; k < 64; ++k) {
+        const unsigned long long dk = readlane64(diag, k);
+        rem |= ((rem >> k) & 1ull) ? 0ull : dk;
+      }
+      const unsigned long long kp = ~rem;
+      if ((kp >> lane) & 1ull) {
+        const int p = cnt + __popcll(kp & lt);
+        if (p < post_n) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) out[(long long)p * 4 + e] = me[e];
+          roi_scores[(long long)b * post_n + p] = scores[(long long)b * cap + i];
+          if (p < NMSB_KEPT_LDS) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) kept[p][e] = me[e];
+          }
+        }
+      }
+      if (lane == 0) kp_sh = kp;
+    }
+    __syncthreads();
+    cnt += __popcll(kp_sh);
+  }
+  if (threadIdx.x == 0) keep_cnt[b] = cnt;
+}
+
+// The coupled truncation: R_b = min(post_n, min over b's segment of the survivor counts); rows R_b .. post_n - 1 are zeroed
+// (rows below R_b were written by the walk, which kept at least R_b boxes).
+__global__ void nms_big_finish_kernel(const int* __restrict__ keep_cnt, int B, int post_n, float* __restrict__ rois,
+                                      float* __restrict__ roi_scores, int* __restrict__ n_out, const int* __restrict__ seg) {
+  const int b = blockIdx.x;
+  int lo, hi, mn = 0x7fffffff;
+  seg_range(seg, B, b, lo, hi);
+  for (int i = lo; i < hi; ++i) mn = min(mn, keep_cnt[i]);
+  const int R = max(min(post_n, mn), 0);
+  if (threadIdx.x == 0) n_out[b] = R;
+  for (int r = R + threadIdx.x; r < post_n; r += blockDim.x) {
+    float* o = rois + ((long long)b * post_n + r) * 4;
+    o[0] = o[1] = o[2] = o[3] = 0.f;
+    roi_scores[(long long)b * post_n + r] = 0.f;
+  }
+}
+
+size_t nms_big_ws_bytes(int B) { return 256 + ((size_t)B * sizeof(int) + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------ RoI pooling (+ positional encoding)
 struct RoiParams {
@@ -650,6 +862,46 @@ extern "C" int nbm_nms_batched(const float* boxes, const float* scores, const in
                      n_in, cap, words, keep_idx, keep_cnt);
   hipLaunchKernelGGL(nms_gather_kernel, dim3(B), dim3(256), 0, st, boxes, scores, keep_idx, keep_cnt, B, cap, post_n,
                      rois, roi_scores, n_out, seg);
+  return nbm_launch_status();
+}
+
+extern "C" int nbm_rpn_select_big_workspace(int B, int cap, int64_t* bytes) {
+  if (!bytes || B <= 0 || cap < 64 || cap > BIG_CAP_MAX || (cap & (cap - 1))) return NBM_EINVAL;
+  *bytes = (int64_t)B * cap * 8;
+  return NBM_OK;
+}
+
+extern "C" int nbm_rpn_select_big(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
+                                  int top_n, int fail_below, int cap, void* ws, int64_t ws_bytes, float* sel_boxes,
+                                  float* sel_scores, int* n_sel, const int* seg, void* stream) {
+  if (!boxes || !keys || !keep_count || !ws || !sel_boxes || !sel_scores || !n_sel || !seg || B <= 0 || KA <= 0)
+    return NBM_EINVAL;
+  if (cap < top_n || cap < 64 || cap > BIG_CAP_MAX || (cap & (cap - 1)) || (((uintptr_t)ws) & 7u) ||
+      ws_bytes < (int64_t)B * cap * 8)
+    return NBM_EINVAL;
+  hipLaunchKernelGGL(rpn_select_big_kernel, dim3(B), dim3(SEL_THREADS), 0, (hipStream_t)stream, boxes, keys, keep_count, B,
+                     KA, top_n, fail_below, cap, static_cast<unsigned long long*>(ws), sel_boxes, sel_scores, n_sel, seg);
+  return nbm_launch_status();
+}
+
+extern "C" int nbm_nms_big_workspace(int B, int cap, int64_t* bytes) {
+  if (!bytes || B <= 0 || cap <= 0 || cap > BIG_CAP_MAX || (cap & 63)) return NBM_EINVAL;
+  *bytes = (int64_t)nms_big_ws_bytes(B);
+  return NBM_OK;
+}
+
+extern "C" int nbm_nms_big(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh,
+                           int post_n, void* ws, int64_t ws_bytes, float* rois, float* roi_scores, int* n_out,
+                           const int* seg, void* stream) {
+  if (!boxes || !scores || !n_in || !ws || !rois || !roi_scores || !n_out || !seg || B <= 0) return NBM_EINVAL;
+  if (cap <= 0 || cap > BIG_CAP_MAX || (cap & 63) || post_n <= 0 || post_n > cap || (((uintptr_t)ws) & 3u) ||
+      ws_bytes < (int64_t)nms_big_ws_bytes(B))
+    return NBM_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  int* keep_cnt = static_cast<int*>(ws);
+  hipLaunchKernelGGL(nms_big_kernel, dim3(B), dim3(NMSB_THREADS), 0, st, boxes, scores, n_in, cap, thresh, post_n, rois,
+                     roi_scores, keep_cnt);
+  hipLaunchKernelGGL(nms_big_finish_kernel, dim3(B), dim3(256), 0, st, keep_cnt, B, post_n, rois, roi_scores, n_out, seg);
   return nbm_launch_status();
 }
 

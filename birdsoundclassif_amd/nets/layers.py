@@ -23,13 +23,6 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
-def _pow2_cap(n):
-    c = 64
-    while c < n:
-        c <<= 1
-    return c
-
-
 class DepthwiseSepConv2d(nn.Module):
     """Inverted depthwise-separable block (reference layers.py:13-46): [bilinear x(1/stride)] -> depthwise 3x3
     (channel multiplier = expansion_fact) -> [FiLM from the positional encoding] -> 1x1 -> BatchNorm -> SiLU."""
@@ -192,8 +185,8 @@ class ProposalLayer(nn.Module):
                                           cfg.min_threshold)
         if images is not None:
             ops.nan_images_fail(images, cnt)
-        cap = _pow2_cap(pre)
-        sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, pre, cfg.rcnn_batch_size, cap, segments=segments)
+        top_n, cap, _ = ops.proposal_plan(pre, keys.shape[1])
+        sb, ss, n_sel = ops.rpn_select(boxes, keys, cnt, top_n, cfg.rcnn_batch_size, cap, segments=segments)
         return ops.nms_batched(sb, ss, n_sel, cfg.nms_thresh, post, segments=segments)
 
     def forward(self, labels_pred, bbox_reg):

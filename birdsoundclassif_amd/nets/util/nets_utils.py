@@ -74,13 +74,14 @@ def setattr_others(args):
 
 def nms(bbox_pred, scores, nms_thresh=0.7, post_nms_topN=300, return_idx=False):
     """Greedy NMS in the given order with the batch-coupled truncation (reference nets_utils.py:210-245),
-    on the device bitmask kernel.  bbox_pred [B,N,4], scores [B,N] (any device; moved to the GPU)."""
+    on the device kernels (`ops.nms_batched`: up to 65536 boxes per image).  bbox_pred [B,N,4], scores [B,N] (any device; moved
+    to the GPU)."""
     from ... import ops
     dev = bbox_pred.device if bbox_pred.is_cuda else torch.device('cuda')
     B, N = scores.shape
     cap = max(64, (N + 63) // 64 * 64)
-    if cap > 4096:
-        raise NotImplementedError('device NMS handles up to 4096 boxes per image')
+    if cap > ops.PROPOSAL_BIG_CAP:
+        raise NotImplementedError(f'device NMS handles up to {ops.PROPOSAL_BIG_CAP} boxes per image, got {N}')
     bx = torch.zeros((B, cap, 4), device=dev, dtype=torch.float32)
     sc = torch.zeros((B, cap), device=dev, dtype=torch.float32)
     bx[:, :N], sc[:, :N] = bbox_pred.to(dev), scores.to(dev)

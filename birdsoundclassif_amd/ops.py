@@ -885,33 +885,81 @@ def roi_counts(n, B, name='n_roi'):
     return _chk_counts(n, B, name)
 
 
-def rpn_select(boxes, keys, keep_count, top_n, fail_below, cap, segments=None):
+PROPOSAL_SMALL_CAP = 4096     # nbm_rpn_select / nbm_nms_batched: sort in LDS, one wave of removed words
+PROPOSAL_BIG_CAP = 65536      # nbm_rpn_select_big / nbm_nms_big
+
+
+def _pow2_cap(n):
+    c = 64
+    while c < n:
+        c <<= 1
+    return c
+
+
+def proposal_plan(pre, KA):
+    """Host-only: the pre-NMS budget `pre` (--pre_nms_topN / --pre_nms_topN_eval) on a map of KA anchors -> (top_n, cap,
+    route).  Up to 4096 the budget is taken as it is, on the kernels that sort in LDS ('small').  A larger one is first cut to
+    KA, which changes no result (an image keeps at most its KA anchors), and goes to the global-memory kernels ('big') when
+    its capacity still exceeds 4096."""
+    pre, KA = int(pre), int(KA)
+    if pre <= PROPOSAL_SMALL_CAP:
+        return pre, _pow2_cap(pre), 'small'
+    top_n = min(pre, KA)
+    cap = _pow2_cap(top_n)
+    if cap <= PROPOSAL_SMALL_CAP:
+        return top_n, cap, 'small'
+    if cap > PROPOSAL_BIG_CAP:
+        raise ValueError(f'--pre_nms_topN / --pre_nms_topN_eval = {pre} on {KA} anchors: the proposal kernels take up to '
+                         f'{PROPOSAL_BIG_CAP} boxes per image')
+    return top_n, cap, 'big'
+
+
+def _workspace(query, B, cap, device, name):
+    nbytes = C.c_int64()
+    check(query(B, cap, C.byref(nbytes)), name)
+    return torch.empty((nbytes.value,), device=device, dtype=torch.uint8), nbytes.value
+
+
+def rpn_select(boxes, keys, keep_count, top_n, fail_below, cap, segments=None, force_big=False):
     """-> sel_boxes [B,cap,4], sel_scores [B,cap], n_sel int32 [B].  The counts are coupled within each segment of `segments`
-    (int32 [2, B] on the device, `segment_table`; None: `batch_segments(B)`, the whole batch)."""
+    (int32 [2, B] on the device, `segment_table`; None: `batch_segments(B)`, the whole batch).  cap above 4096 (up to 65536)
+    runs nbm_rpn_select_big; `force_big` sends a smaller cap there too (tests and benchmarks: the results are the same)."""
     B, KA = keys.shape
     _chk_counts(keep_count, B, 'keep_count')
     segments = batch_segments(B, device=boxes.device) if segments is None else _chk_segments(segments, B)
     sel_boxes = torch.empty((B, cap, 4), device=boxes.device, dtype=torch.float32)
     sel_scores = torch.empty((B, cap), device=boxes.device, dtype=torch.float32)
     n_sel = torch.empty((B,), device=boxes.device, dtype=torch.int32)
+    if cap > PROPOSAL_SMALL_CAP or force_big:
+        ws, ws_bytes = _workspace(lib().nbm_rpn_select_big_workspace, B, cap, boxes.device, 'nbm_rpn_select_big_workspace')
+        check(lib().nbm_rpn_select_big(_ptr(boxes), _ptr(keys), _ptr(keep_count), B, KA, top_n, fail_below, cap, _ptr(ws),
+                                       ws_bytes, _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), _ptr(segments), _stream()),
+              'nbm_rpn_select_big')
+        return sel_boxes, sel_scores, n_sel
     check(lib().nbm_rpn_select(_ptr(boxes), _ptr(keys), _ptr(keep_count), B, KA, top_n, fail_below, cap,
                                _ptr(sel_boxes), _ptr(sel_scores), _ptr(n_sel), _ptr(segments), _stream()), 'nbm_rpn_select')
     return sel_boxes, sel_scores, n_sel
 
 
-def nms_batched(boxes, scores, n_in, thresh, post_n, segments=None):
+def nms_batched(boxes, scores, n_in, thresh, post_n, segments=None, force_big=False):
     """boxes [B,cap,4] in walk order, n_in int32 [B] -> rois [B,post_n,4], scores [B,post_n], n_out int32 [B].  The post-NMS
-    truncation is coupled within each segment (see rpn_select)."""
+    truncation is coupled within each segment (see rpn_select).  cap above 4096 (up to 65536) runs nbm_nms_big, which stores
+    no IoU mask; `force_big` as in rpn_select."""
     _chk(boxes, name='boxes'), _chk(scores, name='scores')
     B, cap = scores.shape
     _chk_counts(n_in, B, 'n_in')
     segments = batch_segments(B, device=boxes.device) if segments is None else _chk_segments(segments, B)
-    words = cap // 64
-    mask_ws = torch.empty((B * cap * words,), device=boxes.device, dtype=torch.int64)
-    keep_ws = torch.empty((B * (cap + 1),), device=boxes.device, dtype=torch.int32)
     rois = torch.empty((B, post_n, 4), device=boxes.device, dtype=torch.float32)
     rs = torch.empty((B, post_n), device=boxes.device, dtype=torch.float32)
     n_out = torch.empty((B,), device=boxes.device, dtype=torch.int32)
+    if cap > PROPOSAL_SMALL_CAP or force_big:
+        ws, ws_bytes = _workspace(lib().nbm_nms_big_workspace, B, cap, boxes.device, 'nbm_nms_big_workspace')
+        check(lib().nbm_nms_big(_ptr(boxes), _ptr(scores), _ptr(n_in), B, cap, float(thresh), post_n, _ptr(ws), ws_bytes,
+                                _ptr(rois), _ptr(rs), _ptr(n_out), _ptr(segments), _stream()), 'nbm_nms_big')
+        return rois, rs, n_out
+    words = cap // 64
+    mask_ws = torch.empty((B * cap * words,), device=boxes.device, dtype=torch.int64)
+    keep_ws = torch.empty((B * (cap + 1),), device=boxes.device, dtype=torch.int32)
     check(lib().nbm_nms_batched(_ptr(boxes), _ptr(scores), _ptr(n_in), B, cap, float(thresh), post_n, _ptr(mask_ws),
                                 _ptr(keep_ws), _ptr(rois), _ptr(rs), _ptr(n_out), _ptr(segments), _stream()), 'nbm_nms_batched')
     return rois, rs, n_out

@@ -466,7 +466,8 @@ int nbm_nan_images(const float* img, int B, int64_t n, int* keep_count, void* st
 
 /* Top-N selection by (score desc, index asc) among kept anchors, N_b = min(top_n, min over b's segment of
  * keep_count); N_b = 0 if < fail_below ("RPN failed", layers.py:287-290).  Writes sel_boxes[b][cap][4],
- * sel_scores[b][cap], n_sel[b] = N_b.  -- layers.py:292-297.  cap >= top_n, cap power of two <= 4096. */
+ * sel_scores[b][cap], n_sel[b] = N_b.  -- layers.py:292-297.  cap >= top_n, cap power of two <= 4096 (the keys are sorted in
+ * LDS; nbm_rpn_select_big below takes larger ones). */
 int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA,
                    int top_n, int fail_below, int cap, float* sel_boxes, float* sel_scores, int* n_sel,
                    const int* seg, void* stream);
@@ -474,10 +475,29 @@ int nbm_rpn_select(const float* boxes, const uint32_t* keys, const int* keep_cou
 /* Greedy NMS in the given order (suppress IoU >= thresh, +1 pixel convention) of the n_in[b] boxes of image b, then
  * the coupled truncation R_b = min(post_n, min over b's segment of #keep) -- nets_utils.py:189-245.
  * Workspaces: mask_ws B*cap*(cap/64) uint64, keep_ws B*(cap+1) int32.  Writes rois[b][post_n][4],
- * roi_scores[b][post_n], n_out[b] = R_b.  cap: multiple of 64, <= 4096. */
+ * roi_scores[b][post_n], n_out[b] = R_b.  cap: multiple of 64, <= 4096 (one wave holds the removed bits; nbm_nms_big below
+ * takes larger ones). */
 int nbm_nms_batched(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh,
                     int post_n, uint64_t* mask_ws, int* keep_ws, float* rois, float* roi_scores, int* n_out,
                     const int* seg, void* stream);
+
+/* The two stages above for up to 65 536 boxes per image (--pre_nms_topN / --pre_nms_topN_eval above 4 096), with the same
+ * contracts and, on any input both take, the same bits.  Kernel launches only: they run inside a captured graph.  The
+ * workspaces may hold stale bytes.
+ * nbm_rpn_select_big: cap >= top_n, cap a power of two in 64 .. 65 536; ws: ws_bytes >= nbm_rpn_select_big_workspace(B, cap)
+ * = 8 * B * cap (the composite keys are sorted in global memory, run by run through LDS), 8-byte aligned.  A segment
+ * minimum above KA is cut to KA. */
+int nbm_rpn_select_big_workspace(int B, int cap, int64_t* bytes);
+int nbm_rpn_select_big(const float* boxes, const uint32_t* keys, const int* keep_count, int B, int KA, int top_n,
+                       int fail_below, int cap, void* ws, int64_t ws_bytes, float* sel_boxes, float* sel_scores,
+                       int* n_sel, const int* seg, void* stream);
+
+/* nbm_nms_big: cap a multiple of 64 up to 65 536, 0 < post_n <= cap, n_in[b] clamped into [0, cap].  No IoU mask is stored:
+ * one workgroup per image walks 64-box blocks and tests each block against the boxes kept so far, and the walk ends at
+ * post_n kept boxes.  ws: ws_bytes >= nbm_nms_big_workspace(B, cap) = one int32 per image + padding, 4-byte aligned. */
+int nbm_nms_big_workspace(int B, int cap, int64_t* bytes);
+int nbm_nms_big(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh, int post_n,
+                void* ws, int64_t ws_bytes, float* rois, float* roi_scores, int* n_out, const int* seg, void* stream);
 
 /* ROIPooling (layers.py:406-497): level assignment, window, 2x2 adaptive average of the FPN map and of
  * the separable positional encoding.  fmaps: 5 device pointers (NHWC, C channels); pe_f [img_h][C/2],
