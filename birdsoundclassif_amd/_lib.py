@@ -41,6 +41,16 @@ class GconvDesc(C.Structure):
                 ('x_ld', C.c_int), ('y_ld', C.c_int), ('relu', C.c_int)]
 
 
+class GconvBwdDesc(C.Structure):
+    """struct nbm_gconv_bwd_desc (include/nbm_hip.h)."""
+    _fields_ = [('g', C.c_void_p), ('y', C.c_void_p), ('w', C.c_void_p), ('x', C.c_void_p), ('out', C.c_void_p),
+                ('scale', C.c_void_p), ('workspace', C.c_void_p), ('workspace_bytes', C.c_longlong),
+                ('B', C.c_int), ('H', C.c_int), ('W', C.c_int), ('groups', C.c_int), ('Cg', C.c_int),
+                ('kh', C.c_int), ('kw', C.c_int), ('stride', C.c_int), ('pad', C.c_int), ('Ho', C.c_int), ('Wo', C.c_int),
+                ('g_ld', C.c_int), ('y_ld', C.c_int), ('x_ld', C.c_int), ('out_ld', C.c_int),
+                ('accumulate', C.c_int), ('splits', C.c_int)]
+
+
 class RoiDesc(C.Structure):
     """struct nbm_roi_desc (include/nbm_hip.h)."""
     _fields_ = [('fmap', C.c_void_p * 5), ('fh', C.c_int * 5), ('fw', C.c_int * 5),
@@ -86,6 +96,9 @@ SIGNATURES = {
     'nbm_copy_rect': [_P, _P, _L, _L, _I, _L, _L, _I, _I, _P],
     'nbm_gemm_conv': [C.POINTER(GemmDesc), _P],
     'nbm_gconv3x3': [C.POINTER(GconvDesc), _P],
+    'nbm_gconv3x3_dgrad': [C.POINTER(GconvBwdDesc), _P],
+    'nbm_gconv3x3_wgrad': [C.POINTER(GconvBwdDesc), _P],
+    'nbm_gconv3x3_wgrad_workspace': [C.POINTER(GconvBwdDesc), C.POINTER(C.c_longlong)],
     'nbm_pcm16_to_wave': [_P, _L, _I, _I, _I, _P, _L, _L, _P, _L, _I, _I, _P],
     'nbm_resample_to_wave': [_P, _L, _I, _L, _I, _I, _P, _I, _L, _L, _P, _L, _I, _I, _I, _P],
     'nbm_wav_decode': [_P, _L, _I, _I, _I, _I, _L, _P, _L, _P],

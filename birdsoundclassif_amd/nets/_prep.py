@@ -65,24 +65,44 @@ def krsc(weight):
     return _cached(weight, 'krsc', make)
 
 
+def _gconv_fragments(weight, groups):
+    C, Cg, kh, kw = weight.shape
+    if (kh, kw) != (3, 3) or C != groups * Cg or 16 % min(Cg, 16) or Cg % 16 not in (0, Cg) or C % 16:
+        raise ValueError(f'gconv: no fragment layout for a {tuple(weight.shape)} weight in {groups} groups')
+    w = weight.reshape(C, Cg, 9)
+    CI = max(Cg, 16)
+    if Cg < 16:
+        # row n of the 16-channel slab that holds its group: columns ci with ci // Cg == (n % 16) // Cg carry W[n][ci % Cg]
+        same = (torch.arange(16, device=w.device)[None, :] // Cg) == ((torch.arange(C, device=w.device) % 16) // Cg)[:, None]
+        w = w.repeat(1, 16 // Cg, 1) * same[:, :, None].to(w.dtype)
+    # [C, CI, 9] -> (t, n % 16, j, q, e, tap) -> (t, tap, j, q, n % 16, e)
+    return w.reshape(C // 16, 16, CI // 16, 4, 4, 9).permute(0, 5, 2, 3, 1, 4).reshape(C // 16, 9, CI // 16, 64, 4).contiguous()
+
+
 def gconv(weight, groups):
     """Grouped 3x3 weights [C, Cg, 3, 3] (checkpoint layout, C = groups * Cg) -> the fragment order of `nbm_gconv3x3`
     (include/nbm_hip.h): [C / 16][9][CI / 16][64][4] with CI = max(Cg, 16), element (t, 3 r + s, j, lane, e) = W[n][ci - g(n) Cg][r][s]
     for n = 16 t + (lane & 15) and the input channel ci = (16 t // CI) CI + 16 j + 4 (lane >> 4) + e when ci lies in n's group g(n),
     else 0 -- groups narrower than 16 channels share a 16 x 16 fragment as a block diagonal."""
+    return _cached(weight, ('gconv', int(groups)), lambda: _gconv_fragments(weight.detach(), groups))
+
+
+def gconv_dgrad(weight, groups, scale=None):
+    """The weights of the DATA-GRADIENT convolution of a grouped 3x3 layer (`nbm_gconv3x3_dgrad`), in the fragment order of `gconv`:
+    transposed inside each group, rotated by 180 degrees, and with the FrozenBN `scale` [C] that multiplies the incoming gradient per
+    output channel folded in (the pattern of `wino23(transposed=True, scale=)`):
+        W'[g Cg + c][n][r][s] = scale[g Cg + n] * W[g Cg + n][c][2 - r][2 - s]."""
     def make():
         C, Cg, kh, kw = weight.shape
-        if (kh, kw) != (3, 3) or C != groups * Cg or 16 % min(Cg, 16) or Cg % 16 not in (0, Cg) or C % 16:
-            raise ValueError(f'gconv: no fragment layout for a {tuple(weight.shape)} weight in {groups} groups')
-        w = weight.detach().reshape(C, Cg, 9)
-        CI = max(Cg, 16)
-        if Cg < 16:
-            # row n of the 16-channel slab that holds its group: columns ci with ci // Cg == (n % 16) // Cg carry W[n][ci % Cg]
-            same = (torch.arange(16, device=w.device)[None, :] // Cg) == ((torch.arange(C, device=w.device) % 16) // Cg)[:, None]
-            w = w.repeat(1, 16 // Cg, 1) * same[:, :, None].to(w.dtype)
-        # [C, CI, 9] -> (t, n % 16, j, q, e, tap) -> (t, tap, j, q, n % 16, e)
-        return w.reshape(C // 16, 16, CI // 16, 4, 4, 9).permute(0, 5, 2, 3, 1, 4).reshape(C // 16, 9, CI // 16, 64, 4).contiguous()
-    return _cached(weight, ('gconv', int(groups)), make)
+        if (kh, kw) != (3, 3) or C != groups * Cg:
+            raise ValueError(f'gconv_dgrad: no fragment layout for a {tuple(weight.shape)} weight in {groups} groups')
+        w = weight.detach().reshape(groups, Cg, Cg, 3, 3)
+        if scale is not None:
+            w = w * scale.detach().reshape(groups, Cg, 1, 1, 1)
+        return _gconv_fragments(w.transpose(1, 2).flip(3, 4).reshape(C, Cg, 3, 3), groups)
+    # the scale's identity belongs to the entry's VERSION, not to its key (see wino23)
+    extra = () if scale is None else (scale.data_ptr(), scale._version)
+    return _cached(weight, ('gconv_dgrad', int(groups), scale is not None), make, extra=extra)
 
 
 def wino23(weight, transposed=False, m=2, scale=None):

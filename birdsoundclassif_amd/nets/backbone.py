@@ -6,7 +6,7 @@ definition (public architecture, reference backbone.py:131 `getattr(torchvision.
 stated here as parameter containers, and the forward is a chain of fp32-MFMA implicit-GEMM launches with
 FrozenBatchNorm affine + ReLU + residual fused into the epilogues.  Activations are NHWC.
 The ResNeXt names (resnext50_32x4d, resnext101_32x8d, resnext101_64x4d) are the same body with grouped bottlenecks, whose 3x3 runs
-on `ops.gconv3x3` (csrc/gconv.hip); they are forward-only.
+on `ops.gconv3x3` (csrc/gconv.hip) and trains through `Fn.GConv3x3` (csrc/gconv_bwd.hip) in training mode.
 """
 import torch
 from torch import nn
@@ -86,8 +86,9 @@ class _Bottleneck(nn.Module):
 class _GroupedBottleneck(nn.Module):
     """ResNeXt bottleneck (torchvision's `Bottleneck` with groups > 1; same module / state_dict names): 1x1 to `width` =
     int(planes * base_width / 64) * groups channels, GROUPED 3x3 (stride on it) through `ops.gconv3x3` with bn2 + ReLU in its epilogue,
-    1x1 to 4 * planes with the shortcut in its epilogue.  Forward only: the grouped convolution has no backward kernels, so the
-    backbone has to be frozen to train what follows it."""
+    1x1 to 4 * planes with the shortcut in its epilogue.  In training mode with a gradient asked for the grouped convolution is the
+    tape node `Fn.GConv3x3` (same forward launch; backward: `ops.gconv3x3_dgrad` / `ops.gconv3x3_wgrad`) between the `Fn.conv` nodes of
+    the 1x1 convolutions; a gradient asked of a block in eval mode is refused."""
 
     def __init__(self, inplanes, planes, stride, downsample, norm_layer, groups, base_width):
         super().__init__()
@@ -103,13 +104,18 @@ class _GroupedBottleneck(nn.Module):
         self.mask_input, self.mask_gy = False, True           # (set by _ResNetBody; only Fn.Bottleneck reads them)
 
     def forward(self, x):
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError('the grouped 3x3 convolution of a ResNeXt block has no backward pass: train with --lr_backbone 0 '
-                                      '(a frozen backbone), or run it under torch.no_grad()')
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if grad and not self.training:
+            raise NotImplementedError('a ResNeXt block in eval mode has no backward pass: call .train() on the model to train through it '
+                                      '(FrozenBN makes the two modes compute the same), or train with --lr_backbone 0 (a frozen '
+                                      'backbone), or run it under torch.no_grad()')
         s, b = self.bn1.affine()
         o = Fn.conv(x, self.conv1.weight, scale=s, shift=b, act=ops.ACT_RELU)
         s, b = self.bn2.affine()
-        o = ops.gconv3x3(o, _prep.gconv(self.conv2.weight, self.groups), self.groups, stride=self.stride, scale=s, shift=b, relu=True)
+        if grad:          # the training chain: the same launch as a tape node (Fn.conv is a tape node already)
+            o = Fn.GConv3x3.apply(o, self.conv2.weight, s, b, self.groups, self.stride)
+        else:
+            o = ops.gconv3x3(o, _prep.gconv(self.conv2.weight, self.groups), self.groups, stride=self.stride, scale=s, shift=b, relu=True)
         if self.downsample is not None:
             s, b = self.downsample[1].affine()
             idt = Fn.conv(x, self.downsample[0].weight, scale=s, shift=b, stride=self.stride)
@@ -206,7 +212,7 @@ class Backbone(BackboneBase):
         super().__init__(_ResNetBody(layers, FrozenBatchNorm2d, dilation=dilation, groups=groups, base_width=base_width), name,
                          in_channels, train_backbone)
         if groups > 1 and not train_backbone and hasattr(self, 'init_conv'):
-            # no gradient passes a grouped block, so none can reach init_conv; its learning rate is --lr_backbone = 0 anyway
+            # a frozen ResNeXt body asks for no gradient, so none reaches init_conv; its learning rate is --lr_backbone = 0 anyway
             self.init_conv.requires_grad_(False)
 
 

@@ -549,6 +549,38 @@ class Bottleneck(Function):
         return (gx, gw1, gw2, gw3, gwd) + (None,) * 11
 
 
+class GConv3x3(Function):
+    """y = relu(scale * gconv3x3(x, W) + shift): the grouped 3x3 convolution of a ResNeXt bottleneck with its folded FrozenBN and ReLU
+    (`ops.gconv3x3`, the launch of the inference chain: the forward values are the same bits).  Backward: `ops.gconv3x3_dgrad` and
+    `ops.gconv3x3_wgrad`, each only when its gradient is asked for; both apply the ReLU mask (y > 0) and the scale themselves."""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, shift, groups, stride):
+        y = ops.gconv3x3(x, _prep.gconv(weight, groups), groups, stride=stride, scale=scale, shift=shift, relu=True)
+        ctx.cfg = (groups, stride)
+        ctx.save_for_backward(x, weight, scale, y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, weight, scale, y = ctx.saved_tensors
+        groups, stride = ctx.cfg
+        gy = gy.contiguous()
+        gx = gw = None
+        if ctx.needs_input_grad[0]:
+            gx = ops.gconv3x3_dgrad(gy, _prep.gconv_dgrad(weight, groups, scale), groups, x.shape[1], x.shape[2], stride=stride, y=y)
+        if ctx.needs_input_grad[1]:
+            C_, Cg = weight.shape[:2]
+            sink = grad_sink(weight, C_, 9 * Cg)
+            if sink is not None:                          # accumulated in place: autograd gets no gradient to add
+                ops.gconv3x3_wgrad(gy, x, groups, stride=stride, scale=scale, y=y, out=sink[0], accumulate=True, channels=C_)
+                sink[1]()
+            else:
+                gw = ops.gconv3x3_wgrad(gy, x, groups, stride=stride, scale=scale, y=y, channels=C_)
+        return gx, gw, None, None, None, None
+
+
 def conv(x, weight, bias=None, scale=None, shift=None, residual=None, kh=1, kw=1, stride=1, pad=0, act=ACT_NONE, alpha=1.0,
          up=None, lazy_stride=None, accept_stash=False):
     """`up` [B,h,w,N]: + bilinear_align_corners(up) in the GEMM epilogue (FPN top-down merge, act must be NONE).

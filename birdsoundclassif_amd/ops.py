@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import GconvDesc, GemmDesc, RoiDesc, check
+from ._lib import GconvBwdDesc, GconvDesc, GemmDesc, RoiDesc, check
 
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_LEAKY = 0, 1, 2, 3
 
@@ -1191,6 +1191,147 @@ def conv_wgrad(g, x, out, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, g_ld=
     if deferred_bias is not None:
         gl = N if g_ld is None else g_ld
         deferred_bias += colsum(g.reshape(-1)[:B * H * W * gl].view(B * H * W, gl), N)
+    return out
+
+
+def _gconv_bwd_desc(B, H, W, groups, Cg, stride, kh=3, kw=3, pad=1, splits=0):
+    d = GconvBwdDesc()
+    d.B, d.H, d.W, d.groups, d.Cg = int(B), int(H), int(W), int(groups), int(Cg)
+    d.kh, d.kw, d.stride, d.pad = int(kh), int(kw), int(stride), int(pad)
+    d.Ho, d.Wo = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+    d.splits = int(splits)
+    return d
+
+
+def _gconv_bwd_operands(name, g, y, groups, C_):
+    """Common checks of the two grouped gradients: g (and y) [B,Ho,Wo,ld >= C], contiguous fp32 on the device."""
+    _chk(g, name='g')
+    if g.dim() != 4 or groups <= 0 or C_ % groups or g.shape[3] < C_:
+        raise ValueError(f'{name}: g must be [B,Ho,Wo,>={C_}] for {groups} groups')
+    if y is not None and (_chk(y, name='y').dim() != 4 or tuple(y.shape[:3]) != tuple(g.shape[:3]) or y.shape[3] < C_):
+        raise ValueError(f'{name}: y must be [{g.shape[0]},{g.shape[1]},{g.shape[2]},>={C_}], the forward output')
+
+
+def gconv_wgrad_plan(B, Ho, Wo, groups, Cg, stride):
+    """Host-only (no GPU needed): what `gconv3x3_wgrad(splits=None)` does for a launch whose gradient map is [B,Ho,Wo,groups * Cg] ->
+    (splits, workspace_bytes).  The library picks the split count (nbm_gconv3x3_wgrad_workspace with splits = 0: two workgroups per
+    CU, at most one per pixel tile, the workspace within the bytes of the two operands); the workspace is linear in it.  The choice
+    depends on the gradient map alone, so the input map is taken as the smallest that gives (Ho, Wo) at this stride."""
+    H, W = (int(Ho) - 1) * int(stride) + 1, (int(Wo) - 1) * int(stride) + 1
+    total, one = C.c_longlong(), C.c_longlong()
+    check(lib().nbm_gconv3x3_wgrad_workspace(C.byref(_gconv_bwd_desc(B, H, W, groups, Cg, stride)), C.byref(total)),
+          'nbm_gconv3x3_wgrad_workspace')
+    check(lib().nbm_gconv3x3_wgrad_workspace(C.byref(_gconv_bwd_desc(B, H, W, groups, Cg, stride, splits=1)), C.byref(one)),
+          'nbm_gconv3x3_wgrad_workspace')
+    return int(total.value // one.value), int(total.value)
+
+
+def gconv3x3_dgrad(g, w_prepared, groups, H, W, stride=1, y=None, out=None, kh=3, kw=3, pad=1):
+    """Data gradient of `gconv3x3` (+ scale + ReLU): g = dL/dy [B,Ho,Wo,g_ld >= C], `w_prepared` = `_prep.gconv_dgrad(weight, groups,
+    scale)`, H x W the forward input map -> gx [B,H,W,C], or into `out` [B,H,W,out_ld >= C] (channels beyond C are left alone).  `y`
+    (the forward output): g counts only where y > 0, applied inside the kernel.  What the kernel does not implement raises (kh, kw and
+    pad are only there to be refused): there is no slow path."""
+    _chk(w_prepared, name='w_prepared')
+    if w_prepared.dim() != 5 or tuple(w_prepared.shape[1::2]) != (9, 64) or w_prepared.shape[4] != 4 or groups <= 0 \
+            or (16 * w_prepared.shape[0]) % groups:
+        raise ValueError('gconv3x3_dgrad: w_prepared must be the output of _prep.gconv_dgrad for these groups')
+    n_ch = 16 * w_prepared.shape[0]
+    Cg = n_ch // groups
+    if max(Cg, 16) != 16 * w_prepared.shape[2]:
+        raise ValueError(f'gconv3x3_dgrad: w_prepared {tuple(w_prepared.shape)} does not belong to {groups} groups of {Cg} channels')
+    _gconv_bwd_operands('gconv3x3_dgrad', g, y, groups, n_ch)
+    B = g.shape[0]
+    d = _gconv_bwd_desc(B, H, W, groups, Cg, stride, kh, kw, pad)
+    if tuple(g.shape[1:3]) != (d.Ho, d.Wo):
+        raise ValueError(f'gconv3x3_dgrad: g is {tuple(g.shape)}, a {H} x {W} input at stride {stride} gives [{B},{d.Ho},{d.Wo},.]')
+    gx = out if out is not None else torch.empty((B, H, W, n_ch), device=g.device, dtype=torch.float32)
+    _chk(gx, name='out')
+    if gx.dim() != 4 or tuple(gx.shape[:3]) != (B, H, W) or gx.shape[3] < n_ch:
+        raise ValueError(f'gconv3x3_dgrad: out must be [{B},{H},{W},>={n_ch}]')
+    d.g, d.w, d.out = g.data_ptr(), w_prepared.data_ptr(), gx.data_ptr()
+    d.g_ld, d.out_ld = g.shape[3], gx.shape[3]
+    if y is not None:
+        d.y, d.y_ld = y.data_ptr(), y.shape[3]
+    if FLOPS is not None:
+        FLOPS[0] += 2.0 * 9 * Cg * n_ch * B * d.Ho * d.Wo         # algorithmic, as gconv3x3
+    with _timed(('gconv_dgrad', B, H, W, Cg, n_ch, kh, stride, groups)):
+        check(lib().nbm_gconv3x3_dgrad(C.byref(d), _stream()), 'nbm_gconv3x3_dgrad')
+    return gx
+
+
+_GCONV_WS = {}
+
+
+def _gconv_workspace(device, nbytes):
+    """One persistent workspace per device and lane (every launch overwrites what it reads; launches of a stream are ordered)."""
+    key = (device, LANE)
+    buf = _GCONV_WS.get(key)
+    if buf is None or buf.numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('the grouped weight-gradient workspace would have to grow during a graph capture')
+        _GCONV_WS[key] = buf = None
+        buf = _GCONV_WS[key] = torch.empty((nbytes,), device=device, dtype=torch.uint8)
+    return buf
+
+
+def gconv3x3_wgrad(g, x, groups, stride=1, scale=None, y=None, out=None, accumulate=False, splits=None, workspace=None,
+                   channels=None, kh=3, kw=3, pad=1):
+    """Weight gradient of `gconv3x3` (+ scale + ReLU): g = dL/dy [B,Ho,Wo,g_ld >= C], x [B,H,W,x_ld >= C] the forward input ->
+    dW [C, Cg, 3, 3] (the parameter's layout), or into `out` (C * Cg * 9 contiguous floats; `accumulate`: added to what is there).
+    `scale` [C] multiplies row n; `y` (the forward output): g counts only where y > 0.  `splits`: workgroups the pixel sum is split over
+    per 64 channels; None takes the library's choice (`gconv_wgrad_plan`), an explicit value (1 .. 4096) is for tests and benchmarks --
+    the result is bitwise reproducible for a given count.  `workspace`: a uint8 tensor for the partial sums (tests); default: a
+    persistent one.  `channels`: C; required where the operands are pitched and neither `out` [C,Cg,3,3] nor `scale` tells it.  What the kernels do
+    not implement raises: there is no slow path."""
+    _chk(x, name='x')
+    if x.dim() != 4 or groups <= 0:
+        raise ValueError('gconv3x3_wgrad: x must be [B,H,W,>=C]')
+    B, H, W, x_ld = x.shape
+    _chk(g, name='g')
+    # C: `channels`, else what `out` [C,Cg,3,3] or `scale` [C] say; unpitched operands of equal width tell it themselves
+    if channels is not None:
+        n_ch = int(channels)
+    elif out is not None and out.dim() == 4:
+        n_ch = out.shape[0]
+    elif scale is not None:
+        n_ch = scale.numel()
+    elif g.shape[-1] == x_ld:
+        n_ch = x_ld
+    else:
+        raise ValueError(f'gconv3x3_wgrad: g and x are {g.shape[-1]} and {x_ld} floats wide: pass `channels` (or `out` [C,Cg,3,3] / `scale`)')
+    _gconv_bwd_operands('gconv3x3_wgrad', g, y, groups, n_ch)
+    Cg = n_ch // groups
+    if x_ld < n_ch or g.shape[0] != B:
+        raise ValueError(f'gconv3x3_wgrad: x {tuple(x.shape)} and g {tuple(g.shape)} do not belong to {n_ch} channels of one batch')
+    d = _gconv_bwd_desc(B, H, W, groups, Cg, stride, kh, kw, pad, splits=0 if splits is None else splits)
+    if splits is not None and not 1 <= int(splits) <= 4096:
+        raise ValueError(f'gconv3x3_wgrad: splits = {splits} (1 .. 4096, or None)')
+    if tuple(g.shape[1:3]) != (d.Ho, d.Wo):
+        raise ValueError(f'gconv3x3_wgrad: g is {tuple(g.shape)}, x {tuple(x.shape)} at stride {stride} gives [{B},{d.Ho},{d.Wo},.]')
+    if scale is not None and _chk(scale, name='scale').numel() != n_ch:
+        raise ValueError(f'gconv3x3_wgrad: scale must hold {n_ch} values')
+    if out is None:
+        if accumulate:
+            raise ValueError('gconv3x3_wgrad: accumulate needs `out`')
+        out = torch.empty((n_ch, Cg, 3, 3), device=x.device, dtype=torch.float32)
+    if _chk(out, name='out').numel() != n_ch * Cg * 9:
+        raise ValueError(f'gconv3x3_wgrad: out must hold [{n_ch},{Cg},3,3]')
+    d.g, d.x, d.out = g.data_ptr(), x.data_ptr(), out.data_ptr()
+    d.g_ld, d.x_ld = g.shape[3], x_ld
+    d.scale = scale.data_ptr() if scale is not None else None
+    if y is not None:
+        d.y, d.y_ld = y.data_ptr(), y.shape[3]
+    d.accumulate = int(bool(accumulate))
+    need = C.c_longlong()
+    check(lib().nbm_gconv3x3_wgrad_workspace(C.byref(d), C.byref(need)), 'nbm_gconv3x3_wgrad_workspace')
+    ws = _gconv_workspace(x.device, need.value) if workspace is None else workspace
+    if not (ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need.value):
+        raise ValueError(f'gconv3x3_wgrad: workspace must be a contiguous uint8 device tensor of at least {need.value} bytes')
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    if FLOPS is not None:
+        FLOPS[0] += 2.0 * 9 * Cg * n_ch * B * d.Ho * d.Wo
+    with _timed(('gconv_wgrad', B, H, W, Cg, n_ch, kh, stride, groups)):
+        check(lib().nbm_gconv3x3_wgrad(C.byref(d), _stream()), 'nbm_gconv3x3_wgrad')
     return out
 
 

@@ -138,6 +138,54 @@ typedef struct nbm_gconv_desc {
 } nbm_gconv_desc;
 int nbm_gconv3x3(const nbm_gconv_desc* d, void* stream);
 
+/* Gradients of nbm_gconv3x3 followed by the folded FrozenBatchNorm2d + ReLU, y = relu(scale * gconv(x, W) + shift) (csrc/gconv_bwd.hip;
+ * same geometry: 3x3, pad 1, stride 1 or 2, NHWC fp32, Cg in {4, 8, 16, 32, 64}, C = groups * Cg a multiple of 64, pitched pixels).
+ * g = dL/dy [B][Ho][Wo][C]; both kernels use dz = g * (y > 0), the mask applied while the operand is staged (y optional: without it
+ * g is used as it is), and scale[n] enters through the prepared weights (data gradient) or the reduction (weight gradient).
+ *
+ * nbm_gconv3x3_dgrad:  out = gx [B][H][W] pixels of out_ld floats,
+ *   gx[b][iy][ix][g*Cg + c] = sum over n < Cg and the taps (r, s) with (iy + 1 - r) and (ix + 1 - s) divisible by stride of
+ *                             dz[b][(iy+1-r)/stride][(ix+1-s)/stride][g*Cg + n] * scale[g*Cg + n] * W[g*Cg + n][c][r][s]
+ *   (positions outside [0,Ho) x [0,Wo) count as zero; H and W are given because at stride 2 Ho does not determine H).  w is the
+ *   PREPARED weight `_prep.gconv_dgrad(weight, groups, scale)`: the fragments (layout of nbm_gconv3x3) of
+ *   W'[g*Cg + c][n][r][s] = scale[g*Cg + n] * W[g*Cg + n][c][2-r][2-s].  x, scale, workspace, accumulate and splits are not read.
+ *
+ * nbm_gconv3x3_wgrad:  out = dW [C][Cg][3][3], the parameter's own layout (C rows of 9 Cg floats, 4-byte aligned),
+ *   dW[g*Cg + n][c][r][s] (+)= scale[g*Cg + n] * sum over b, oy, ox of dz[b][oy][ox][g*Cg + n] * x[b][oy*stride-1+r][ox*stride-1+s][g*Cg + c]
+ *   (`accumulate`: added to what is there; scale optional).  The sum over the pixels is split over `splits` workgroups per 64 channels
+ *   (0: the library's choice, 1 .. 4096: as given); every split stores its partial fragments to `workspace` (at least the bytes
+ *   nbm_gconv3x3_wgrad_workspace returns for the same descriptor, 16-byte aligned; its previous contents are not read) and a second
+ *   kernel sums them in ascending order and is the only writer of dW: no atomics, the same bits every run.  w is not read.
+ *
+ * nbm_gconv3x3_wgrad_workspace: host only, no HIP call; *bytes = splits * C * 9 * max(Cg, 16) * 4 with the split count the launch
+ *   will use (pointers of the descriptor are not looked at).
+ *
+ * Anything outside the geometry, a pointer that is not 16-byte aligned or a pitch that is no multiple of 4 returns NBM_EUNSUPPORTED and
+ * launches nothing: there is no slow path.  Nothing is allocated inside.
+ *
+ * Replaces: what autograd derives for reference train.py:212 `losses.backward()` through the grouped `conv2` + bn2 + ReLU of
+ *   torchvision's ResNeXt Bottleneck (backbone.py:131 `getattr(torchvision.models, name)`): d/d(input) and d/d(conv2.weight). */
+typedef struct nbm_gconv_bwd_desc {
+  const float* g;        /* dL/dy, [B][Ho][Wo] pixels of g_ld floats                        */
+  const float* y;        /* forward output (ReLU mask), pixels of y_ld floats, or NULL      */
+  const float* w;        /* dgrad: prepared weights, see above                              */
+  const float* x;        /* wgrad: forward input, [B][H][W] pixels of x_ld floats           */
+  float* out;            /* dgrad: gx, pixels of out_ld floats; wgrad: dW [C][Cg*9]         */
+  const float* scale;    /* wgrad: [C] or NULL                                              */
+  void* workspace;       /* wgrad: partial fragments of the splits                          */
+  long long workspace_bytes;
+  int B, H, W;
+  int groups, Cg;
+  int kh, kw, stride, pad;
+  int Ho, Wo;            /* (H - 1) / stride + 1, (W - 1) / stride + 1                      */
+  int g_ld, y_ld, x_ld, out_ld;
+  int accumulate;        /* wgrad: dW += instead of dW =                                    */
+  int splits;            /* wgrad: 0 = the library's choice                                 */
+} nbm_gconv_bwd_desc;
+int nbm_gconv3x3_dgrad(const nbm_gconv_bwd_desc* d, void* stream);
+int nbm_gconv3x3_wgrad(const nbm_gconv_bwd_desc* d, void* stream);
+int nbm_gconv3x3_wgrad_workspace(const nbm_gconv_bwd_desc* d, long long* bytes);
+
 /* Winograd transforms for 3x3 / stride 1 / pad 1 convolutions (the FPN output convolutions, fpn.py:137,145, and their data /
  * weight gradients).  m = 2: F(2x2,3x3), 16 transformed planes, used by the forward pass (error ~3e-6, proposals stay
  * bit-identical to the reference); m = 4: F(4x4,3x3) with interpolation points {0, 1, -1, 1/2, -2, inf}, 36 planes, used by
