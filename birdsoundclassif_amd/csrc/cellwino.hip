@@ -227,6 +227,82 @@ __global__ __launch_bounds__(256) void cell_input_up_kernel(const float* __restr
   }
 }
 
+// Column window of cell column ox under the interpolation above: the in-image pixels of a patch row (columns S*ox-2 .. S*ox+2) read the
+// source columns x0(l), x1(l) -- with a ratio of about 1/2 at most four consecutive ones.  -> first column; `used`: bit s = column
+// xb + s is read by an in-image pixel.  Same fp32 expressions on the host (the launcher's check, `_prep.xfold_columns`).
+__host__ __device__ inline int cell_col_window(int ox, int S, int W, int Wc, float sw, unsigned& used) {
+#pragma clang fp contract(off)
+  int xb = 0x7fffffff, x0s[NP];
+  for (int l = 0; l < NP; ++l) {
+    const int xx = S * ox - 2 + l;
+    const int xc = xx < 0 ? 0 : (xx > W - 1 ? W - 1 : xx);
+    const float fx = sw * xc;
+    x0s[l] = (int)fx;
+    if ((unsigned)xx < (unsigned)W && x0s[l] < xb) xb = x0s[l];
+  }
+  used = 0u;
+  for (int l = 0; l < NP; ++l)
+    if ((unsigned)(S * ox - 2 + l) < (unsigned)W) {
+      const int d0 = x0s[l] - xb, d1 = d0 + (x0s[l] < Wc - 1 ? 1 : 0);
+      used |= (1u << (d0 < 31 ? d0 : 31)) | (1u << (d1 < 31 ? d1 : 31));
+    }
+  return xb;
+}
+
+// The patches of cell_input_up_kernel<RAW> BEFORE their horizontal interpolation: the five pixels of a patch row are fixed combinations
+// (per cell column) of the window's four source columns, and everything behind the patches is linear -- the combination lives in the
+// weights (`_prep.rpn_composite_xfold`), 20 planes instead of 25.  Plane 4 j + s of cell (b, oy, ox) =
+//   D = (hy * x1[y0][xb + s] + ly * x1[y1][xb + s]) + bias      (row arithmetic as above; 0 where patch row j lies outside the image
+//                                                                or no in-image pixel of the row reads column xb + s)
+// Vx [OW][20][B * OH][C]: the cells of one column are the rows of one GEMM group, a group's planes lie (B * OH) x C floats apart.
+__global__ __launch_bounds__(256) void cell_patches_up_cols_kernel(const float* __restrict__ x1, const float* __restrict__ bias,
+                                                                   const CellGeom q, int Hc, int Wc, float sh, float sw,
+                                                                   float* __restrict__ Vx) {
+#pragma clang fp contract(off)
+  constexpr int NS = 4;
+  const f32x4* s4 = reinterpret_cast<const f32x4*>(x1);
+  f32x4* v4 = reinterpret_cast<f32x4*>(Vx);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const unsigned total = (unsigned)(q.T * q.C4);
+  const long long rows = (long long)q.B * q.OH;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    const int c = (int)(i % (unsigned)q.C4);
+    const unsigned cell = i / (unsigned)q.C4;
+    int b, oy, ox;
+    cell_of(q, cell, b, oy, ox);
+    const f32x4 bv = bias ? reinterpret_cast<const f32x4*>(bias)[c] : zero;
+    unsigned used;
+    const int xb = cell_col_window(ox, q.S, q.W, Wc, sw, used);
+    const long long rb = (long long)b * Hc;
+    const long long out0 = ((long long)ox * (NP * NS) * rows + (long long)b * q.OH + oy) * q.C4 + c;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const int y = q.S * oy - 2 + j;
+      const bool yin = (unsigned)y < (unsigned)q.H;
+      const float fy = sh * (yin ? y : 0);
+      const int y0 = (int)fy, y1 = y0 + (y0 < Hc - 1 ? 1 : 0);
+      const float ly = fminf(fmaxf(fy - y0, 0.f), 1.f), hy = 1.f - ly;
+      // the 8 loads of a patch row go out together (an unused column reads a clamped address and is zeroed afterwards)
+      f32x4 v0[NS], v1[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const int xs = min(xb + s, Wc - 1);
+        v0[s] = s4[((rb + y0) * Wc + xs) * q.C4 + c];
+        v1[s] = s4[((rb + y1) * Wc + xs) * q.C4 + c];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const bool ok = yin && ((used >> s) & 1u);
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = ok ? (hy * v0[s][e] + ly * v1[s][e]) + bv[e] : 0.f;
+        v4[out0 + (long long)(j * NS + s) * rows * q.C4] = v;
+      }
+    }
+  }
+}
+
 // M [25][T][C] -> gx [B][H][W][C]: patch = Vinv M Vinv^T written to the 5x5 pixels of the cell that lie inside the image
 // (cls < 0, S >= 5: patches of different cells do not overlap); the rest of gx is not touched.
 // cls = 0..3 (S >= 3): only the cells with (oy & 1, ox & 1) == (cls >> 1, cls & 1), and the patch is ADDED to gx -- cells of one
@@ -512,6 +588,22 @@ extern "C" int nbm_cell_patches_up(const float* x1, const float* bias, int B, in
   const float sh = H > 1 ? (float)(Hc - 1) / (float)(H - 1) : 0.f, sw = W > 1 ? (float)(Wc - 1) / (float)(W - 1) : 0.f;
   hipLaunchKernelGGL(cell_input_up_kernel<true>, dim3(stream_grid(q.T * q.C4, q.C4)), dim3(256), 0, (hipStream_t)stream, x1, bias, q, Hc, Wc,
                      sh, sw, Vx, ld / 4, c_off / 4);
+  return nbm_launch_status();
+}
+
+extern "C" int nbm_cell_patches_up_cols(const float* x1, const float* bias, int B, int H, int W, int C, int Hc, int Wc, int stride, float* Vx,
+                                        void* stream) {
+  CellGeom q;
+  if (!x1 || !Vx || !cell_geom(B, H, W, C, stride, q) || Hc <= 0 || Wc <= 0) return NBM_EINVAL;
+  if (!nbm_aligned16(x1) || !nbm_aligned16(Vx) || (bias && !nbm_aligned16(bias))) return NBM_EALIGN;
+  const float sh = H > 1 ? (float)(Hc - 1) / (float)(H - 1) : 0.f, sw = W > 1 ? (float)(Wc - 1) / (float)(W - 1) : 0.f;
+  for (int ox = 0; ox < q.OW; ++ox) {          // a window wider than four columns has no place in the 20 planes
+    unsigned used;
+    cell_col_window(ox, stride, W, Wc, sw, used);
+    if (used >> 4) return NBM_EUNSUPPORTED;
+  }
+  hipLaunchKernelGGL(cell_patches_up_cols_kernel, dim3(stream_grid(q.T * q.C4, q.C4)), dim3(256), 0, (hipStream_t)stream, x1, bias, q, Hc,
+                     Wc, sh, sw, Vx);
   return nbm_launch_status();
 }
 

@@ -254,6 +254,102 @@ def rpn_composite_delta(out_w, out_b, dw_w, dw_b, pt_w, scale, shift, rmask, sma
                    extra=_rpn_extra(out_b, dw_w, dw_b, pt_w, scale, shift, lat_wk, alpha))
 
 
+XFOLD_COLS = 4      # source columns per cell column that `nbm_cell_patches_up_cols` writes
+_XFOLD_GEOM = {}
+
+
+def xfold_columns(W, Wc, S):
+    """The horizontal half of the align-corners bilinear top-down merge (fpn.py:143-144) seen from the cell columns of a 3x3 / stride S /
+    pad 1 reader composed with a 3x3 in front of it: the five pixels x = S ox - 2 + l of a patch row read source columns x0(l), x1(l) of
+    the Wc-wide coarse map with weights hx, lx -- the fp32 expressions of `cell_input_up_kernel` (fx = sw * clamp(x), x0 = (int) fx,
+    x1 = x0 + (x0 < Wc - 1), lx = clamp(fx - x0), hx = 1 - lx), evaluated here in numpy float32.  A pixel outside the image reads
+    nothing; x0 == x1 puts both weights on one column.
+    -> (xbase int [OW]: the first column any in-image pixel of cell column ox reads; used bool [OW][4]: the window's columns that are
+        read; cx float64 [OW][5][4]: pixel l = sum_s cx[ox][l][s] * column xbase[ox] + s), or None when some cell column reads more than
+    XFOLD_COLS consecutive columns (a ratio far from 1/2)."""
+    import numpy as np
+    key = (int(W), int(Wc), int(S))
+    if key not in _XFOLD_GEOM:
+        OW = (W - 1) // S + 1
+        f32 = np.float32
+        sw = f32(Wc - 1) / f32(W - 1) if W > 1 else f32(0.0)
+        x = S * np.arange(OW)[:, None] - 2 + np.arange(5)[None, :]                      # [OW][5]
+        inside = (x >= 0) & (x < W)
+        fx = sw * np.clip(x, 0, W - 1).astype(f32)
+        assert fx.dtype == np.float32
+        x0 = fx.astype(np.int64)
+        x1 = x0 + (x0 < Wc - 1)
+        lx = np.minimum(np.maximum(fx - x0.astype(f32), f32(0.0)), f32(1.0))
+        hx = f32(1.0) - lx
+        xbase = np.where(inside, x0, np.iinfo(np.int64).max).min(1)
+        hit = None
+        if int(np.where(inside, x1 - xbase[:, None], 0).max()) < XFOLD_COLS:
+            cx = np.zeros((OW, 5, XFOLD_COLS), dtype=np.float64)
+            used = np.zeros((OW, XFOLD_COLS), dtype=bool)
+            for ox in range(OW):
+                for l in range(5):
+                    if inside[ox, l]:
+                        cx[ox, l, x0[ox, l] - xbase[ox]] += float(hx[ox, l])
+                        cx[ox, l, x1[ox, l] - xbase[ox]] += float(lx[ox, l])
+                        used[ox, x0[ox, l] - xbase[ox]] = used[ox, x1[ox, l] - xbase[ox]] = True
+            hit = (xbase, used, cx)
+        _XFOLD_GEOM[key] = hit
+    return _XFOLD_GEOM[key]
+
+
+def xfold64(we, cx):
+    """float64: we [N][R][5][C] (R patch rows of 5 pixels) and cx [G][5][4] of `xfold_columns` ->
+    Wf [G][N][R][4][C] = sum_l cx[g][l][s] we[n][r][l][c]: the weights of the window's columns instead of the row's pixels."""
+    return torch.einsum('gls,nrlc->gnrsc', cx, we)
+
+
+def rpn_composite_xfold(out_w, out_b, dw_w, dw_b, pt_w, scale, shift, W, Wc, S, smasks, rows=None, lat_wk=None, alpha=1.0):
+    """The interpolated operand's share of `rpn_composite` (channels [0, C) of K: up(x1) + b behind a deferred lateral) with the
+    horizontal interpolation folded into the weights, for `nbm_cell_patches_up_cols`' operand: one weight matrix per cell column ox,
+    built from the weights of that column's OWN class (`smasks[ox]`: its depthwise tap columns inside the map) -- the left column's
+    border difference is in its group's weights.
+    rows = None -> [OW][N][20 C] (plane-major K: 4 j + s), the cells whose depthwise tap rows all lie inside the map.
+    rows = (rmask, (a, ...)) -> [len(a)][OW][N][4 C]: scale * (W(rmask, smask) - W(7, smask)) on the listed patch rows -- what a row of
+    border cells adds to the former (`rpn_composite_delta` for the grouped operand).  float64 arithmetic, once per weight version and
+    geometry; None when `xfold_columns` has no window."""
+    geom = xfold_columns(W, Wc, S)
+    if geom is None:
+        return None
+    smasks = tuple(int(s) for s in smasks)
+    c = out_w.shape[1]
+
+    def make():
+        cx = torch.from_numpy(geom[2]).to(out_w.device)
+        n = pt_w.shape[0]
+        a_rows = list(range(5)) if rows is None else list(rows[1])
+        out = torch.empty((len(smasks), n, len(a_rows), XFOLD_COLS * c), dtype=torch.float32, device=out_w.device)
+        for sm in sorted(set(smasks)):
+            we = _rpn_composite64(out_w, out_b, dw_w, dw_b, pt_w, 7, sm, lat_wk, alpha)[0][..., :c]
+            if rows is not None:
+                we = (_rpn_composite64(out_w, out_b, dw_w, dw_b, pt_w, rows[0], sm, lat_wk, alpha)[0][..., :c] - we) * \
+                    scale.double()[:, None, None, None]
+            we = we[:, a_rows]
+            oxs = [ox for ox, s in enumerate(smasks) if s == sm]
+            for i in range(0, len(oxs), 8):                              # (a float64 copy of the whole result would be 1 GB at 188 x 512)
+                sel = torch.tensor(oxs[i:i + 8], device=out_w.device)
+                out[sel] = xfold64(we, cx[sel]).reshape(len(sel), n, len(a_rows), -1).float()
+        if rows is None:
+            return out.reshape(len(smasks), n, -1)
+        return out.permute(2, 0, 1, 3).contiguous()
+    tag = ('rpnxf', int(W), int(Wc), int(S), smasks, None if rows is None else (int(rows[0]), tuple(rows[1])), lat_wk is not None)
+    return _cached(out_w, tag, make, extra=_rpn_extra(out_b, dw_w, dw_b, pt_w, scale, shift, lat_wk, alpha))
+
+
+def rpn_composite_delta_part(out_w, out_b, dw_w, dw_b, pt_w, scale, shift, rmask, smask, taps, c0, c1, lat_wk=None, alpha=1.0):
+    """`rpn_composite_delta` for channels [c0, c1) of K alone: (dw [N][len(taps) * (c1 - c0)], dshift [N])."""
+    def make():
+        d, dsh = rpn_composite_delta(out_w, out_b, dw_w, dw_b, pt_w, scale, shift, rmask, smask, taps, lat_wk=lat_wk, alpha=alpha)
+        d = d.reshape(d.shape[0], len(taps), -1)[:, :, c0:c1]
+        return d.reshape(d.shape[0], -1).contiguous(), dsh
+    return _cached(out_w, ('rpndp', int(rmask), int(smask), tuple(taps), int(c0), int(c1), lat_wk is not None), make,
+                   extra=_rpn_extra(out_b, dw_w, dw_b, pt_w, scale, shift, lat_wk, alpha))
+
+
 def lateral_of_projection(lat_w, lat_b, proj_w, proj_b):
     """FPN lateral 1x1 (fpn.py:143) applied to `fm + final_projection(ctx)` (self_attention.py:55,76) without forming that sum:
     lateral(fm + W_o ctx + b_o) = W_l fm + (W_l W_o) ctx + (W_l b_o + b_l).  -> (W_l W_o as KRSC rows [N][d], shift [N]); float64

@@ -21,6 +21,9 @@ from .ops import check, lib, _ptr, _chk, _stream, gemm_conv, conv_wgrad
 
 LAZY_FINEST = os.environ.get('NBM_LAZY_FINEST', '1') != '0'
 COMPOSITE = os.environ.get('NBM_RPN_COMPOSITE', '1') != '0'     # evaluation mode: the RPN's reader composed with this convolution (rpn_composite)
+# ... with the horizontal half of the top-down interpolation folded into its weights (20 patch planes instead of 25)
+XFOLD = os.environ.get('NBM_RPN_XFOLD', '1') != '0'
+XFOLD_CALLS = [0]                   # tests: batch chunks that took the folded route
 TRAIN_COMPOSITE = os.environ.get('NBM_RPN_COMPOSITE_TRAIN', '1') != '0'   # training: the same composition in the cell domain (train_composite_*)
 # The deferred lateral's OWN gradients from the consumer's backward pass: its pattern share rides in the cell-domain GEMMs (the
 # folded weights [U | alpha U W] give d/dt in the transform domain, the weight-gradient GEMMs already hold d/d(alpha U W)), its RoI
@@ -497,6 +500,15 @@ def _border_classes(nb, H, W, S, device):
     return hit
 
 
+def _xfold_applies(nb, OH, OW, C_):
+    """The folded route runs one GEMM group per cell column, nb * OH rows each: a group's four planes of one patch row must lie inside the
+    2 GB window of a buffer resource (14 000 images of the 188 x 512 level; the batch chunks are far smaller).  Nothing else about the
+    batch decides: the two routes round differently, and a clip's bits must not depend on how many clips share its batch -- so NOT the
+    padded tile count either (OW groups padded to 128 rows each are more tiles than one group at 9 images and fewer; such grids are
+    smaller than one round of workgroups over the CUs, where the 4/5 K of every tile is what the launch takes)."""
+    return 4 * nb * OH * C_ * 4 < (1 << 31) - (1 << 24)
+
+
 def rpn_composite(fm, block):
     """Evaluation mode: the output of `block` (layers.DepthwiseSepConv2d, the RPN's reader of the map: depthwise 3x3 / stride S ->
     1x1 -> BatchNorm -> SiLU) on the demand-driven map `fm` WITHOUT the map's pattern pixels: the block composed with the map's own
@@ -505,7 +517,10 @@ def rpn_composite(fm, block):
     no depthwise pass and no 1x1 behind it.  An operand that exists as a dense map (the merged map of a level whose pattern covers every
     pixel; the lateral's input t of a deferred lateral) is gathered by the implicit GEMM itself, in channel slices; the interpolated
     operand of a deferred lateral (up(x1) + b, position-dependent weights: not a convolution of x1) goes through raw 5x5 patches
-    (nbm_cell_patches_up: [25][cells][C], 25 taps) and one launch per patch row.  The launches are chained through the residual input
+    (nbm_cell_patches_up: [25][cells][C], 25 taps) and one launch per patch row -- or, where a patch row's five pixels read at most four
+    source columns (a ratio of about 1/2; XFOLD), through those columns before their horizontal interpolation, which then lives in the
+    weights of the cell column (nbm_cell_patches_up_cols: [OW][20][nb * OH][C]; grouped launches, one group per cell column).
+    The launches are chained through the residual input
     (y = scale * acc + [shift + R | y]; SiLU on the last): a single fmaf chain over all 25 K products rounds 25 K times against a running
     sum that has grown to the whole result -- measured 1.5 x the rms error of the route through the pattern pixels; 3-6 shorter chains
     are below it.  Border cells (a depthwise tap in the zero padding of the map) differ from the interior in a handful of taps: their
@@ -547,12 +562,25 @@ def rpn_composite(fm, block):
     ws, sc, sh = prep.rpn_composite(*wargs, **wkw, parts=parts)
     f = torch.empty((B, OH, OW, N2), device=fm.device, dtype=torch.float32)
     stream = _stream()
+    # the interpolated operand without its horizontal interpolation (`_xfold_applies`): 20 planes, one GEMM group per cell column
+    xfold_ok = bool(XFOLD and lt is not None and direct_t and C_ % 32 == 0 and N2 % 4 == 0 and
+                    prep.xfold_columns(W, lt.up.shape[2], S) is not None)
+    rmasks, smasks = _tap_masks(H, W, S)
     keep_label, ops._PROFILE_LABEL = ops._PROFILE_LABEL, ('rpn-composite', H, W)
     try:
         for (b0, nb, pat) in st.chunks:
             T = nb * OH * OW
             V = None
-            if KV:
+            fold = xfold_ok and _xfold_applies(nb, OH, OW, C_)
+            if fold:
+                XFOLD_CALLS[0] += 1
+                NC = prep.XFOLD_COLS
+                rows_g = nb * OH                                # rows of a cell column's group; a plane of the group: rows_g * C_ floats
+                V = ops._wino_scratch(fm.device, 5 * NC * T * C_, 0)[0]
+                check(lib().nbm_cell_patches_up_cols(_ptr(lt.up[b0:b0 + nb]), _ptr(lt.bias), nb, H, W, C_, lt.up.shape[1], lt.up.shape[2], S,
+                                                     _ptr(V), stream), 'nbm_cell_patches_up_cols')
+                wf = prep.rpn_composite_xfold(*wargs, W, lt.up.shape[2], S, smasks, **wkw)           # [OW][N][20 C]
+            elif KV:
                 V = ops._wino_scratch(fm.device, 25 * T * KV, 0)[0]
                 if lt is not None:
                     check(lib().nbm_cell_patches_up(_ptr(lt.up[b0:b0 + nb]), _ptr(lt.bias), nb, H, W, C_, lt.up.shape[1], lt.up.shape[2], S,
@@ -568,14 +596,21 @@ def rpn_composite(fm, block):
             R = None
             if border:
                 R = torch.zeros((T, N2), device=fm.device, dtype=torch.float32)
-                Vv = V[:25 * T * KV].view(25, T, KV) if KV else None
+                Vv = V[:25 * T * KV].view(25, T, KV) if KV and not fold else None
+                # folded operand: its border share is in the group weights (columns) and in the row launches below; the classes' constants
+                # and the other operands' share stay here
+                b_ops = [op for op in operands if not (fold and op[0] == 'patch')]
+                Kb = K - C_ if fold else K
                 for rmask, smask, taps, tap_idx, idx, pix in border:
                     if not taps:
                         continue
-                    dwt, dsh = prep.rpn_composite_delta(*wargs, rmask, smask, taps, **wkw)
+                    if fold:
+                        dwt, dsh = prep.rpn_composite_delta_part(*wargs, rmask, smask, taps, C_, K, **wkw)
+                    else:
+                        dwt, dsh = prep.rpn_composite_delta(*wargs, rmask, smask, taps, **wkw)
                     Tb, nt = idx.numel(), len(taps)
                     cols = []                                   # the class's operand rows [taps, cells, K], gathered piece by piece
-                    for op in operands:
+                    for op in b_ops:
                         if op[0] == 'patch':
                             cols.append(Vv[tap_idx, idx[None, :]])
                         else:
@@ -589,16 +624,39 @@ def rpn_composite(fm, block):
                     # few rows, a long K: 32-column slices as groups (128 x 32 tiles: a quarter of the serial MFMA work per K-step of
                     # the 128 x 128 tile; 150 -> ~35 us per class); the shift comes in through the residual input, which has a group stride
                     if N2 % 32 == 0:
-                        gemm_conv(Vb, dwt, fb, B=1, H=nt, W=Tb, Cin=K, N=32, kh=nt, kw=1, Ho=1, Wo=Tb, x_ld=K, w_ld=nt * K, y_ld=N2,
-                                  groups=N2 // 32, x_gs=0, w_gs=32 * nt * K, y_gs=32, residual=dsh.expand(Tb, N2).contiguous(), res_ld=N2,
+                        gemm_conv(Vb, dwt, fb, B=1, H=nt, W=Tb, Cin=Kb, N=32, kh=nt, kw=1, Ho=1, Wo=Tb, x_ld=Kb, w_ld=nt * Kb, y_ld=N2,
+                                  groups=N2 // 32, x_gs=0, w_gs=32 * nt * Kb, y_gs=32, residual=dsh.expand(Tb, N2).contiguous(), res_ld=N2,
                                   res_gs=32)
                     else:
-                        gemm_conv(Vb, dwt, fb, B=1, H=nt, W=Tb, Cin=K, N=N2, kh=nt, kw=1, Ho=1, Wo=Tb, x_ld=K, w_ld=nt * K, shift=dsh)
+                        gemm_conv(Vb, dwt, fb, B=1, H=nt, W=Tb, Cin=Kb, N=N2, kh=nt, kw=1, Ho=1, Wo=Tb, x_ld=Kb, w_ld=nt * Kb, shift=dsh)
                     R.index_copy_(0, idx, fb)
+                if fold:
+                    # a row of border cells (a depthwise tap ROW in the padding): W(row class, column class) - W(interior rows, column class)
+                    # differs on the patch rows the dropped tap rows reach -- one grouped launch per such row that holds data, on the rows
+                    # b * OH + oy of every group, added to R in place (the BatchNorm scale is folded in)
+                    for oy in range(OH):
+                        if rmasks[oy] == 7:
+                            continue
+                        a_rows = tuple(a for a in range(5) if 0 <= S * oy - 2 + a < H and
+                                       any(0 <= a - r <= 2 for r in range(3) if not (rmasks[oy] >> r) & 1))
+                        dwf = prep.rpn_composite_xfold(*wargs, W, lt.up.shape[2], S, smasks, rows=(rmasks[oy], a_rows), **wkw)
+                        Ro = R[oy * OW:]
+                        ops._PROFILE_LABEL = ('rpn-composite', H, W, 'cols')
+                        for i, a in enumerate(a_rows):
+                            gemm_conv(V[(a * NC * rows_g + oy) * C_:], dwf[i], Ro, B=1, H=NC, W=nb, Cin=C_, N=N2, kh=NC, kw=1, Ho=1, Wo=nb,
+                                      x_ld=OH * C_, w_ld=NC * C_, y_ld=OH * OW * N2, groups=OW, x_gs=5 * NC * rows_g * C_,
+                                      w_gs=N2 * NC * C_, y_gs=N2, residual=Ro, res_ld=OH * OW * N2, res_gs=N2)
             # the chain of launches
             links = []
             for op, w in zip(operands, ws):
-                if op[0] == 'patch':
+                if op[0] == 'patch' and fold:
+                    # one launch per patch row (4 window columns x C_), grouped over the cell columns: group ox reads its own rows of V and
+                    # its own weights and writes column ox of the [nb * OH, OW, N2] output
+                    for j in range(5):
+                        links.append(dict(x=V[j * NC * rows_g * C_:], w=wf[:, :, j * NC * C_:], B=1, H=NC, W=rows_g, Cin=C_, kh=NC, kw=1, Ho=1,
+                                          Wo=rows_g, x_ld=C_, w_ld=5 * NC * C_, groups=OW, x_gs=5 * NC * rows_g * C_, w_gs=N2 * 5 * NC * C_,
+                                          y_gs=N2, y_ld=OW * N2, res_gs=N2, res_ld=OW * N2))
+                elif op[0] == 'patch':
                     # one launch per patch ROW (5 taps x KV); a tap's plane lies (tap index) x T x KV floats behind the first -- groups of
                     # planes whose offsets stay inside the 2 GB window of a buffer resource
                     ppl = max(1, min(5, ((1 << 31) - (1 << 24)) // (T * KV * 4)))
@@ -613,9 +671,11 @@ def rpn_composite(fm, block):
                                       x_ld=m_.shape[-1], w_ld=25 * cw))
             for i, ln in enumerate(links):
                 res = R if i == 0 else fc
-                ops._PROFILE_LABEL = ('rpn-composite' if ln['kw'] == 1 else 'rpn-composite-map', H, W)
+                # (a fourth field marks the grouped form for the per-launch tables)
+                ops._PROFILE_LABEL = ('rpn-composite' if ln['kw'] == 1 else 'rpn-composite-map', H, W) + (('cols',) if 'groups' in ln else ())
+                res_ld = ln.pop('res_ld', N2)
                 gemm_conv(ln.pop('x'), ln.pop('w'), fc, N=N2, scale=sc, shift=sh if i == 0 else None, residual=res,
-                          res_ld=N2 if res is not None else None, act=ops.ACT_SILU if i == len(links) - 1 else ops.ACT_NONE, **ln)
+                          res_ld=res_ld if res is not None else None, act=ops.ACT_SILU if i == len(links) - 1 else ops.ACT_NONE, **ln)
     finally:
         ops._PROFILE_LABEL = keep_label
     return f

@@ -304,6 +304,13 @@ int nbm_cell_input_up(const float* x1, const float* bias, int B, int H, int W, i
 int nbm_cell_patches(const float* x, int B, int H, int W, int C, int stride, float* Vx, int ld, int c_off, void* stream);
 int nbm_cell_patches_up(const float* x1, const float* bias, int B, int H, int W, int C, int Hc, int Wc, int stride, float* Vx, int ld,
                         int c_off, void* stream);
+/* nbm_cell_patches_up before its horizontal interpolation: with a ratio of about 1/2 the five pixels of a patch row read at
+ * most four consecutive columns xb(ox) .. xb(ox) + 3 of x1, in combinations that depend on the cell column ox alone and that the
+ * consumer holds in its weights.  Vx [OW][20][B * OH][C], plane 4 j + s of cell (b, oy, ox) at row b * OH + oy of group ox:
+ * (hy x1[y0][xb + s] + ly x1[y1][xb + s]) + bias with the row arithmetic of nbm_cell_patches_up; 0 where patch row j lies outside the
+ * image or no in-image pixel of the row reads that column.  NBM_EUNSUPPORTED when some cell column's window is wider than four. */
+int nbm_cell_patches_up_cols(const float* x1, const float* bias, int B, int H, int W, int C, int Hc, int Wc, int stride, float* Vx,
+                             void* stream);
 
 /* Rectangle copy between a strided array and packed rows (no counterpart in the reference: plumbing of the composed RPN reader in
  * training mode, DESIGN 4h -- the border-cell classes of reference layers.py:22-29's depthwise padding are rectangles [r0, r1) x [c0, c1)

@@ -60,8 +60,11 @@ for tag, ms in rows:
     if label is not None and label[0] == 'rpn-composite':
         what = (f'{k} of the 25 taps of the RPN reader composed with the 3x3 in front of it, 5x5 {Cin}->{N} @{label[1]}x{label[2]} over {W} cells '
                 '(evaluation mode: no pattern pixels; nbm_cell_patches is a separate HBM-bound kernel, not in this table)')
-        fl = 2.0 * W * N * Cin * k / 1e9
-        by = 4.0 * (k * W * Cin + 2 * W * N + N * Cin * k) / 1e9
+        if len(label) > 3:       # the column-window operand: one group per cell column, its own weights
+            what = (f'{k} of the 20 column-window planes of the same reader, {G} cell columns x {W} rows, weights per column, '
+                    f'{Cin}->{N} @{label[1]}x{label[2]} (nbm_cell_patches_up_cols is a separate HBM-bound kernel, not in this table)')
+        fl = 2.0 * G * W * N * Cin * k / 1e9
+        by = 4.0 * G * (k * W * Cin + 2 * W * N + N * Cin * k) / 1e9
         tot += ms
         print(f'{ms:8.3f}  {fl / ms:8.1f}  {by / ms * 1e3:9.0f}   {what}')
         continue
