@@ -19,8 +19,7 @@
 // of one M-tile, which share the gathered A rows, run on the same XCD.
 #include <stdlib.h>
 #include "nbm_common.h"
-#include "igemm_params.h"
-#include "igemm_plan.h"
+#include "igemm_device.h"
 #include <type_traits>
 
 namespace {
@@ -29,7 +28,6 @@ constexpr int BK = 32;
 constexpr int PITCH = 36;  // floats per LDS row (32 + 4 pad)
 
 enum { A_FAST = 0, A_GENERIC = 1 };
-enum { EPI_STD = 0 };
 
 using nbm_igemm::IgemmParams;
 
@@ -58,16 +56,14 @@ __global__ __launch_bounds__(256, BM > 128 ? 1 : STAGES == 1 ? 3 : 2) void igemm
   constexpr int WAVES_N = BN / WN;
   constexpr int AR = BM / 32, BR = BN / 32;  // rows per thread in the staging pass
   static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
+  static_assert(EPI == EPI_STD, "EPI is reserved: the instantiation names carry it");
 
   __shared__ __attribute__((aligned(16))) float lds[STAGES * (BM + BN) * PITCH];
   if constexpr (STAGES == 2) nbm_stagger_priority();
   float* As = lds;                       // [STAGES][BM][PITCH]
   float* Bs = lds + STAGES * BM * PITCH; // [STAGES][BN][PITCH]
 
-  // ---- XCD-aware tile id (bijective for any grid size)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(gridDim.x, blockIdx.x);
   int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   // dense pixel index of GEMM row m, or -1 (ROWS only)
   auto row_pixel = [&](int m) -> long long {
@@ -83,9 +79,9 @@ __global__ __launch_bounds__(256, BM > 128 ? 1 : STAGES == 1 ? 3 : 2) void igemm
   };
   if constexpr (ROWS) {
     if (p.rows_blocks) {          // device-side count: the filled blocks lead; spread them over the XCDs (see wino_fused.hip)
-      const int j = bid >> 3;
+      const int j = blockIdx.x >> 3;
       tile_n = j % p.n_tiles;
-      tile_m = (j / p.n_tiles) * 8 + xcd;
+      tile_m = (j / p.n_tiles) * 8 + (blockIdx.x & 7);
       if (tile_m >= p.m_tiles || tile_m * (BM / 128) >= *p.rows_blocks * (p.rows_mode == 2 ? 16 : 1)) return;
     }
     if (p.rows[p.rows_mode == 2 ? (tile_m * BM) >> 4 : tile_m * BM] < 0) return;       // an empty block (lists are -1 padded at the end)
@@ -105,9 +101,7 @@ __global__ __launch_bounds__(256, BM > 128 ? 1 : STAGES == 1 ? 3 : 2) void igemm
   long long a_base[AR];
   int a_iy0[AR], a_ix0[AR];
   bool a_ok[AR];
-  // FAST path: per-row 32-bit offsets relative to a block-uniform (scalar) base, and one bit per filter tap that says
-  // whether the tap lands inside the image -- the K loop then needs one add and one bit test per row instead of
-  // re-deriving coordinates (the address/validity VALU work sat in front of every MFMA burst: 15 % of the kernel).
+  // FAST path: per-row offsets relative to a block-uniform (scalar) base and tap masks (gather_row, igemm_device.h)
   unsigned a_rel[AR];
   unsigned long long a_taps[AR];
   long long blk_base = 0;
@@ -116,38 +110,32 @@ __global__ __launch_bounds__(256, BM > 128 ? 1 : STAGES == 1 ? 3 : 2) void igemm
     const int b = (int)nbm_fdiv((unsigned)e0, p.rows_mode == 2 ? p.fd_rows_thw : p.fd_howo);
     blk_base = (long long)b * p.HoWo * p.x_ld;
   } else {
-    const int m0 = bm0 < p.M ? bm0 : 0;
-    const int b = (int)nbm_fdiv((unsigned)m0, p.fd_howo), rem = m0 - b * p.HoWo;
-    const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
-    blk_base = ((long long)(b * p.H + oy * p.stride - p.pad) * p.W + (ox * p.stride - p.pad)) * p.x_ld;
+    blk_base = gather_base(p, bm0);
   }
 #pragma unroll
   for (int i = 0; i < AR; ++i) {
     const int m = bm0 + r0 + 32 * i;
     a_ok[i] = m < p.M;
-    long long mm = a_ok[i] ? m : 0;
-    if constexpr (ROWS) {
-      if (a_ok[i]) { mm = row_pixel(m); a_ok[i] = mm >= 0; }
-      if (!a_ok[i]) mm = blk_base / p.x_ld;
+    if constexpr (AMODE == A_FAST && !ROWS) {
+      const GatherRow gr = gather_row(p, m, a_ok[i], blk_base, c4 * 4);
+      a_rel[i] = gr.rel;
+      a_taps[i] = gr.taps;
+    } else {      // GENERIC keeps coordinates and a 64-bit base per row; ROWS decodes the listed pixel
+      long long mm = a_ok[i] ? m : 0;
+      if constexpr (ROWS) {
+        if (a_ok[i]) { mm = row_pixel(m); a_ok[i] = mm >= 0; }
+        if (!a_ok[i]) mm = blk_base / p.x_ld;
+      }
+      const int b = (int)nbm_fdiv((unsigned)mm, p.fd_howo), rem = (int)(mm - (long long)b * p.HoWo);
+      const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
+      a_iy0[i] = oy * p.stride - p.pad;
+      a_ix0[i] = ox * p.stride - p.pad;
+      a_base[i] = ((long long)(b * p.H + a_iy0[i]) * p.W + a_ix0[i]) * p.x_ld;
+      a_rel[i] = ((unsigned)(a_base[i] - blk_base) + c4 * 4) * 4u;   // bytes; rows ascend with m: never negative
+      unsigned long long mk = 0ull;
+      if constexpr (AMODE == A_FAST) mk = tap_mask(p, a_iy0[i], a_ix0[i]);
+      a_taps[i] = a_ok[i] ? mk : 0ull;
     }
-    // (pixel indices fit 31 bits: M is an int; a 64-bit division here was ~150 instructions per row)
-    const int b = (int)nbm_fdiv((unsigned)mm, p.fd_howo), rem = (int)(mm - (long long)b * p.HoWo);
-    const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
-    a_iy0[i] = oy * p.stride - p.pad;
-    a_ix0[i] = ox * p.stride - p.pad;
-    a_base[i] = ((long long)(b * p.H + a_iy0[i]) * p.W + a_ix0[i]) * p.x_ld;
-    a_rel[i] = ((unsigned)(a_base[i] - blk_base) + c4 * 4) * 4u;   // bytes; rows ascend with m: never negative
-    unsigned long long mk = 0ull;
-    if constexpr (AMODE == A_FAST) {
-      // rows and columns of the filter that land inside the image, then their product -- selects only: as a kh x kw nest of data-dependent
-      // branches this loop was the longest part of the tile prologue (cycle counters of the data-gradient twin, round 5)
-      unsigned rowm = 0u, colm = 0u;
-      for (int r = 0; r < p.kh; ++r) rowm |= ((unsigned)(a_iy0[i] + r) < (unsigned)p.H ? 1u : 0u) << r;
-      for (int s2 = 0; s2 < p.kw; ++s2) colm |= ((unsigned)(a_ix0[i] + s2) < (unsigned)p.W ? 1u : 0u) << s2;
-      for (int r = 0; r < p.kh; ++r) mk |= ((rowm >> r) & 1u) ? (unsigned long long)colm << (r * p.kw) : 0ull;
-      mk = a_ok[i] ? mk : 0ull;
-    }
-    a_taps[i] = mk;
   }
   const float* b_ptr[BR];
   bool b_ok[BR];
@@ -160,8 +148,8 @@ __global__ __launch_bounds__(256, BM > 128 ? 1 : STAGES == 1 ? 3 : 2) void igemm
     b_rel[i] = b_ok[i] ? (unsigned)(n * p.w_ld + c4 * 4) * 4u : 0x80000000u;   // bytes, or out of range
   }
   // raw buffer resources (stride 0, 2 GB window): base = block-uniform pointer, range check gives the zero padding
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xg + blk_base), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wgp), 0, 0x7ffffff0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(xg + blk_base, 0x7ffffff0u);
+  const __amdgpu_buffer_rsrc_t rsrc_b = make_rsrc(wgp, 0x7ffffff0u);
 
   f32x4 ra[AR], rb[BR];
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -311,9 +299,7 @@ __global__ __launch_bounds__(256, BM > 128 ? 1 : STAGES == 1 ? 3 : 2) void igemm
   }
   __syncthreads();
 
-#define NBM_EPI_LDS_FLOATS (STAGES * (BM + BN) * PITCH)
-#include "igemm_epilogue.inc"
-#undef NBM_EPI_LDS_FLOATS
+  igemm_store_tile<BM, BN, WM, WN, STAGES, ROWS, STAGES * (BM + BN) * PITCH>(p, g, lds, acc, bm0, bn0, wm0, wn0, lrow, lh, tid, row_pixel);
 }
 
 // ---- streaming 1x1 (stride 1) for the layers whose whole weight matrix fits LDS (N * K <= 16 K: ResNet layer1's 64 -> 64 / 64 -> 256 /
@@ -445,7 +431,7 @@ __global__ __launch_bounds__(WAVES * 64, 1) void stream1x1_kernel(const StreamPa
           }
         }
       }
-      // epilogue, one 32 x 32 block at a time through this wave's LDS patch (same arithmetic as the tiled kernel's)
+      // epilogue, one 32 x 32 block at a time through this wave's LDS patch (the tiled kernel's arithmetic: igemm_device.h)
 #pragma unroll
       for (int j = 0; j < NTG; ++j) {
         const int jj = g * NTG + j;
@@ -461,26 +447,11 @@ __global__ __launch_bounds__(WAVES * 64, 1) void stream1x1_kernel(const StreamPa
         for (int pass = 0; pass < 4; ++pass) {
           const int r = pass * 8 + er, m = m0 + r;
           if (m >= p.M) continue;
-          f32x4 v = *reinterpret_cast<const f32x4*>(stg + r * SPITCH + ec);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (v[e] * p.alpha) * sc[e] + sh[e] + 0.f;
+          f32x4 v = epi_affine4(*reinterpret_cast<const f32x4*>(stg + r * SPITCH + ec), p.alpha, sc, sh, 0.f);
           if (p.residual) { v[0] += rq[j][pass][0]; v[1] += rq[j][pass][1]; v[2] += rq[j][pass][2]; v[3] += rq[j][pass][3]; }
-          if (p.act == NBM_ACT_RELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
-          } else if (p.act == NBM_ACT_SILU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] / (1.0f + expf(-v[e]));
-          } else if (p.act == NBM_ACT_LEAKY) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.01f * v[e];
-          }
+          v = epi_act4(v, p.act);
           if (p.bits_out) {                          // the 8 lanes of a row (er) hold its 32 channels of block jj: one word
-            const int grp8 = 8 * er;                 // this row's byte of the wave-wide comparison masks: bit 8 e + q <-> channel 4 q + e
-            const unsigned wb = ((unsigned)(__builtin_amdgcn_ballot_w64(v[0] > 0.f) >> grp8) & 0xffu) |
-                                (((unsigned)(__builtin_amdgcn_ballot_w64(v[1] > 0.f) >> grp8) & 0xffu) << 8) |
-                                (((unsigned)(__builtin_amdgcn_ballot_w64(v[2] > 0.f) >> grp8) & 0xffu) << 16) |
-                                (((unsigned)(__builtin_amdgcn_ballot_w64(v[3] > 0.f) >> grp8) & 0xffu) << 24);
+            const unsigned wb = epi_relu_bits(v, 8 * er);
             if (ec == 0) Bw[wave][r * NT + jj] = wb;        // written out row-contiguous once the tile is complete (below)
           }
           *reinterpret_cast<f32x4*>(p.y + (long long)m * p.y_ld + n) = v;

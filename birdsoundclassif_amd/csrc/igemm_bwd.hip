@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include "nbm_common.h"
 #include "igemm_split_tn.h"
+#include "igemm_device.h"
 #include <type_traits>
 
 namespace {
@@ -54,16 +55,8 @@ struct BwdParams {
   nbm_fastdiv fd_howo, fd_wo;   // TN: output pixels per image, output row width
 };
 
-__device__ __forceinline__ int xcd_tile(int nwg, int bid) {
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-}
-
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, unsigned bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, bytes, 0x00020000);
 }
 
 // ---------------------------------------------------------------------------------------------------- NN

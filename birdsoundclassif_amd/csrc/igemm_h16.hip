@@ -12,7 +12,7 @@
 // 8..15: its two groups are q = 2h, 2h + 1 of the full step -- the same pairs in the same sequence, the same bits.
 #include <stdlib.h>
 #include "nbm_common.h"
-#include "igemm_params.h"
+#include "igemm_device.h"
 #include <type_traits>
 
 namespace {
@@ -20,25 +20,18 @@ namespace {
 using nbm_igemm::IgemmParams;
 constexpr int BM = 128, BN = 128, WM = 64, WN = 64, MT = 2, NT = 2;
 constexpr int P16 = 20;      // floats per LDS row (16 + 4 pad: conflict-free ds_read_b128 of 16 consecutive rows)
-enum { EPI_STD = 0 };
 
 __global__ __launch_bounds__(256, 3) void igemm_h16_kernel(const IgemmParams p) {
-  constexpr int STAGES = 1, EPI = EPI_STD;          // (names the shared epilogue text expects: the tile goes out in two halves)
-  constexpr bool ROWS = false;
   __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * P16];
   float* As = lds;                   // [2][BM][P16]
   float* Bs = lds + 2 * BM * P16;    // [2][BN][P16]
 
-  // ---- XCD-aware tile id (bijective for any grid size), as in igemm.hip
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(gridDim.x, blockIdx.x);
   const int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   const int bm0 = tile_m * BM, bn0 = tile_n * BN;
   const int g = blockIdx.z;
   const float* __restrict__ xg = p.x + (long long)g * p.x_gs;
   const float* __restrict__ wgp = p.w + (long long)g * p.w_gs;
-  auto row_pixel = [&](int m) -> long long { return m; };      // (ROWS form of the epilogue text: unused)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
@@ -48,36 +41,20 @@ __global__ __launch_bounds__(256, 3) void igemm_h16_kernel(const IgemmParams p) 
   // chunk c holds k = koff .. koff + 3 (+ 8 for the second half-step) of the 32-wide step
   const int c = tid & 3, r0 = tid >> 2;
   const int koff = c < 2 ? 4 * c : 16 + 4 * (c - 2);
-  long long blk_base;
-  {
-    const int m0 = bm0 < p.M ? bm0 : 0;
-    const int b = (int)nbm_fdiv((unsigned)m0, p.fd_howo), rem = m0 - b * p.HoWo;
-    const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
-    blk_base = ((long long)(b * p.H + oy * p.stride - p.pad) * p.W + (ox * p.stride - p.pad)) * p.x_ld;
-  }
+  const long long blk_base = gather_base(p, bm0);
   unsigned a_rel[2], b_rel[2];
   unsigned long long a_taps[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = bm0 + r0 + 64 * i;
-    const bool ok = m < p.M;
-    const int mm = ok ? m : 0;
-    const int b = (int)nbm_fdiv((unsigned)mm, p.fd_howo), rem = mm - b * p.HoWo;
-    const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
-    const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-    const long long base = ((long long)(b * p.H + iy0) * p.W + ix0) * p.x_ld;
-    a_rel[i] = ((unsigned)(base - blk_base) + koff) * 4u;        // bytes; rows ascend with m: never negative
-    unsigned rowm = 0u, colm = 0u;
-    unsigned long long mk = 0ull;
-    for (int r = 0; r < p.kh; ++r) rowm |= ((unsigned)(iy0 + r) < (unsigned)p.H ? 1u : 0u) << r;
-    for (int s2 = 0; s2 < p.kw; ++s2) colm |= ((unsigned)(ix0 + s2) < (unsigned)p.W ? 1u : 0u) << s2;
-    for (int r = 0; r < p.kh; ++r) mk |= ((rowm >> r) & 1u) ? (unsigned long long)colm << (r * p.kw) : 0ull;
-    a_taps[i] = ok ? mk : 0ull;
+    const GatherRow gr = gather_row(p, m, m < p.M, blk_base, koff);
+    a_rel[i] = gr.rel;
+    a_taps[i] = gr.taps;
     const int n = bn0 + r0 + 64 * i;
     b_rel[i] = n < p.N ? (unsigned)(n * p.w_ld + koff) * 4u : 0x80000000u;
   }
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xg + blk_base), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wgp), 0, 0x7ffffff0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(xg + blk_base, 0x7ffffff0u);
+  const __amdgpu_buffer_rsrc_t rsrc_b = make_rsrc(wgp, 0x7ffffff0u);
 
   f32x4 ra[2], rb[2];
   // cursor of the next half-step to load: filter tap (channel chunk OUTER, tap INNER like igemm.hip), first channel of the 32-wide step, half
@@ -175,9 +152,8 @@ __global__ __launch_bounds__(256, 3) void igemm_h16_kernel(const IgemmParams p) 
   }
   __syncthreads();
 
-#define NBM_EPI_LDS_FLOATS (2 * (BM + BN) * P16)
-#include "igemm_epilogue.inc"
-#undef NBM_EPI_LDS_FLOATS
+  // STAGES = 1: the tile goes out in two halves, like the single-stage form's
+  igemm_store_tile<BM, BN, WM, WN, 1, false, 2 * (BM + BN) * P16>(p, g, lds, acc, bm0, bn0, wm0, wn0, lrow, lh, tid);
 }
 
 }  // namespace

@@ -20,11 +20,11 @@
 //   * the split is a stream of single vector instructions (11 per pair of floats); a stage's 48 MFMA gaps are three runs of 16, one per
 //     chunk of 8 floats: 11 gaps with four split instructions (and at most one fragment read), 3 with one plane write, 2 with one
 //     buffer load -- a 32x32x16 MFMA hides ~5 single-issue fillers of its own wave, a ds_write_b128 costs 13 cycles of issue
-//     (/opt/skills/guides/MI355X_MICROARCH.md, cycle constants) -- and `sched_barrier` pins every gap.
+//     (MI355X_MICROARCH, cycle constants) -- and `sched_barrier` pins every gap.
 // The gather (A from the NHWC activation, taps inner, channel chunks outer; W in KRSC) and the epilogue are those of igemm.hip.
 #include <stdlib.h>
 #include "nbm_common.h"
-#include "igemm_params.h"
+#include "igemm_device.h"
 #include <type_traits>
 #include <utility>
 
@@ -34,7 +34,6 @@ using nbm_igemm::IgemmParams;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
-constexpr int PITCH = 36;                           // (epilogue text only)
 constexpr int BM = 256, BN = 128, WM = 128, WN = 64, MT = 4, NT = 2;
 constexpr int TROWS = BM + BN, CH = TROWS / 128;    // staging chunks (row, 8 floats) per thread and K16 stage
 constexpr int PLANE = TROWS * 32;                   // bytes per bf16 plane of one stage
@@ -42,28 +41,21 @@ constexpr int STAGE = 3 * PLANE;
 constexpr int NBUF = 3;
 constexpr int UOPS = CH * 4 * 11;                   // split micro-ops per stage and thread
 constexpr int NM = MT * NT * 6;                     // MFMAs per stage and wave
-enum { EPI_STD = 0 };
 
 template <int N> using I = std::integral_constant<int, N>;
 __device__ inline int slot(int row, int half) { return row * 32 + ((half ^ ((row >> 3) & 1)) << 4); }
 
 template <int REM>
 __global__ __launch_bounds__(256, 1) void igemm_split_kernel(const IgemmParams p) {
-  constexpr int STAGES = 2, EPI = EPI_STD;          // (names the shared epilogue text expects)
-  constexpr bool ROWS = false;
   __shared__ __attribute__((aligned(16))) float lds[NBUF * STAGE / 4];
   unsigned char* const ldsb = reinterpret_cast<unsigned char*>(lds);
 
-  // ---- XCD-aware tile id (bijective for any grid size), as in igemm.hip
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(gridDim.x, blockIdx.x);
   const int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   const int bm0 = tile_m * BM, bn0 = tile_n * BN;
   const int g = blockIdx.z;
   const float* __restrict__ xg = p.x + (long long)g * p.x_gs;
   const float* __restrict__ wgp = p.w + (long long)g * p.w_gs;
-  auto row_pixel = [&](int m) -> long long { return m; };      // (ROWS form of the epilogue text: unused)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
@@ -71,32 +63,16 @@ __global__ __launch_bounds__(256, 1) void igemm_split_kernel(const IgemmParams p
 
   // ---- staging assignment: thread -> rows (tid >> 1) + 128 c (c = 0, 1: A rows, c = 2: W row), 8-float chunk e of the stage's 16
   const int e = tid & 1, r0 = tid >> 1;
-  long long blk_base;
-  {
-    const int m0 = bm0 < p.M ? bm0 : 0;
-    const int b = (int)nbm_fdiv((unsigned)m0, p.fd_howo), rem = m0 - b * p.HoWo;
-    const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
-    blk_base = ((long long)(b * p.H + oy * p.stride - p.pad) * p.W + (ox * p.stride - p.pad)) * p.x_ld;
-  }
+  const long long blk_base = gather_base(p, bm0);
   unsigned rel[CH];                                  // byte offset of the chunk inside its buffer resource (A: relative to blk_base)
   unsigned long long taps[CH - 1];                   // A rows: one bit per filter tap that lands inside the image
   int wofs[CH];
 #pragma unroll
   for (int c = 0; c < CH - 1; ++c) {
     const int m = bm0 + r0 + 128 * c;
-    const bool ok = m < p.M;
-    const long long mm = ok ? m : 0;
-    const int b = (int)nbm_fdiv((unsigned)mm, p.fd_howo), rem = (int)(mm - (long long)b * p.HoWo);
-    const int oy = (int)nbm_fdiv((unsigned)rem, p.fd_wo), ox = rem - oy * p.Wo;
-    const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-    const long long base = ((long long)(b * p.H + iy0) * p.W + ix0) * p.x_ld;
-    rel[c] = ((unsigned)(base - blk_base) + e * 8) * 4u;       // rows ascend with m: never negative
-    unsigned long long mk = 0ull;
-    unsigned rowm = 0u, colm = 0u;                     // (selects only, as in igemm.hip)
-    for (int r = 0; r < p.kh; ++r) rowm |= ((unsigned)(iy0 + r) < (unsigned)p.H ? 1u : 0u) << r;
-    for (int s2 = 0; s2 < p.kw; ++s2) colm |= ((unsigned)(ix0 + s2) < (unsigned)p.W ? 1u : 0u) << s2;
-    for (int r = 0; r < p.kh; ++r) mk |= ((rowm >> r) & 1u) ? (unsigned long long)colm << (r * p.kw) : 0ull;
-    taps[c] = ok ? mk : 0ull;
+    const GatherRow gr = gather_row(p, m, m < p.M, blk_base, e * 8);
+    rel[c] = gr.rel;
+    taps[c] = gr.taps;
     wofs[c] = slot(r0 + 128 * c, e);
   }
   {
@@ -104,8 +80,8 @@ __global__ __launch_bounds__(256, 1) void igemm_split_kernel(const IgemmParams p
     rel[CH - 1] = n < p.N ? (unsigned)(n * p.w_ld + e * 8) * 4u : 0x80000000u;
     wofs[CH - 1] = slot(BM + r0, e);
   }
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xg + blk_base), 0, 0x7ffffff0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wgp), 0, 0x7ffffff0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(xg + blk_base, 0x7ffffff0u);
+  const __amdgpu_buffer_rsrc_t rsrc_b = make_rsrc(wgp, 0x7ffffff0u);
   int a_ofs[MT], b_ofs[NT];
 #pragma unroll
   for (int i = 0; i < MT; ++i) a_ofs[i] = slot(wm0 + 32 * i + lrow, lh);
@@ -270,14 +246,16 @@ __global__ __launch_bounds__(256, 1) void igemm_split_kernel(const IgemmParams p
       for (int q = 0; q < 16; ++q) acc[i][j][q] += lo[i][j][q];
   __syncthreads();
 
-#define NBM_EPI_LDS_FLOATS (NBUF * STAGE / 4)
-#include "igemm_epilogue.inc"
-#undef NBM_EPI_LDS_FLOATS
+  // a 256-row tile goes out 128 rows at a time.  plan_fwd sends only 16-byte epilogues here (fast_vec): said to the compiler, because the
+  // scalar store path's 128 rows of addresses per lane do not fit beside 256 accumulator registers (scratch)
+  __builtin_assume(p.vec_epi != 0);
+  igemm_store_tile<BM, BN, WM, WN, 2, false, NBUF * STAGE / 4>(p, g, lds, acc, bm0, bn0, wm0, wn0, lrow, lh, tid);
 }
 
 }  // namespace
 
 int nbm_igemm::split_launch(const IgemmParams& p, const GemmPlan& pl, hipStream_t st) {
+  if (!pl.vec_epi) return NBM_EUNSUPPORTED;      // the kernel assumes the 16-byte epilogue (plan_fwd: deep K implies it)
   const dim3 grid(pl.grid[0], pl.grid[1], pl.grid[2]);
   switch (pl.kernel) {
     case K_FWD_SPLIT_R0: hipLaunchKernelGGL((igemm_split_kernel<0>), grid, dim3(256), 0, st, p); break;

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include "nbm_common.h"
 #include "igemm_split_tn.h"
+#include "igemm_device.h"
 #include <type_traits>
 #include <utility>
 
@@ -41,10 +42,7 @@ __global__ __launch_bounds__(256, 1) void igemm_split_tn_kernel(const SplitTnPar
   __shared__ __attribute__((aligned(16))) float lds[NBUF * STAGE / 4];
   unsigned char* const ldsb = reinterpret_cast<unsigned char*>(lds);
 
-  // ---- XCD-aware tile id (bijective for any grid size), as in igemm.hip
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(gridDim.x, blockIdx.x);
   const int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   const int bm0 = tile_m * BM, bn0 = tile_n * BN;     // first dW row n, first dW column k of the tile
   const int g = blockIdx.z;
@@ -96,8 +94,8 @@ __global__ __launch_bounds__(256, 1) void igemm_split_tn_kernel(const SplitTnPar
     long long rows = (ld_t < S) ? (long long)p.M - mb : 0;
     rows = rows < 0 ? 0 : (rows > 16 ? 16 : rows);
     const long long mbs = rows > 0 ? mb : 0;         // (an empty resource never touches memory; keep its base inside the tensor anyway)
-    rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gg + mbs * p.g_ld), 0, (int)(rows * p.g_ld * 4), 0x00020000);
-    rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xg + mbs * p.x_ld), 0, (int)(rows * p.x_ld * 4), 0x00020000);
+    rsrc_a = make_rsrc(gg + mbs * p.g_ld, (unsigned)(rows * p.g_ld * 4));
+    rsrc_b = make_rsrc(xg + mbs * p.x_ld, (unsigned)(rows * p.x_ld * 4));
   };
   auto cursor_next = [&]() { ++ld_t; cursor_set(); };
   float raw[3][CH][8];                               // raw data of stage t lives in slot t % 3

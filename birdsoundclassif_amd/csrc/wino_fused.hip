@@ -20,6 +20,7 @@
 // Two shapes: BN = 128 (wave tile 64 x 64: 64 scratch + 256 output accumulator registers, ONE wave per SIMD) and BN = 64
 // (wave tile 64 x 32: 32 + 128, two workgroups per CU like igemm.hip).
 #include "nbm_common.h"
+#include "igemm_device.h"
 #include <type_traits>
 
 namespace {
@@ -141,17 +142,15 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
   float* Bs = lds + 2 * BM * PITCH;
 
   // ---- XCD-aware tile id (bijective for any grid size): the N tiles of one M tile share an L2
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_tile(gridDim.x, blockIdx.x);
   int tile_m = wg / p.n_tiles, tile_n = wg - tile_m * p.n_tiles;
   if (p.n_blocks) {
     // device-side block count: only the leading blocks are filled, and the contiguous ranges above would put all of them on
     // one XCD (measured: the RoI launch ran on an eighth of the chip).  Round-robin the M blocks over the XCDs instead; the N
     // tiles of a block stay on its XCD, back to back.  The grid is padded to a multiple of 8 * n_tiles.
-    const int j = bid >> 3;
+    const int j = blockIdx.x >> 3;
     tile_n = j % p.n_tiles;
-    tile_m = (j / p.n_tiles) * 8 + xcd;
+    tile_m = (j / p.n_tiles) * 8 + (blockIdx.x & 7);
     if (tile_m >= p.m_tiles) return;
   }
   const int bm0 = tile_m * BM, bn0 = tile_n * BN;
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
     b_rel[i] = n < p.N ? (unsigned)((n * p.C + c4 * 4) * 4) : 0x80000000u;
   }
   const float* a_plane0 = p.R + blk_base;
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.U), 0, 0x7ffffff0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_b = make_rsrc(p.U, 0x7ffffff0u);
 
   f32x4 ra[AR], ra2[AR], rb[BR];
   float a_sign = 1.f;             // sign of the second column of the tile being staged
@@ -208,8 +207,7 @@ __global__ __launch_bounds__(256, BN == 128 ? 1 : 2) void wino23_fused_kernel(co
   auto load_tiles = [&]() {
     const int i = ld_xi >> 2, j = ld_xi & 3;
     const int k1 = j == 0 ? 0 : (j == 2 ? 2 : 1), k2 = j == 2 ? 1 : (j == 3 ? 3 : 2);
-    const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(a_plane0 + (long long)i * p.r_gs), 0, 0x7ffffff0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_a = make_rsrc(a_plane0 + (long long)i * p.r_gs, 0x7ffffff0u);
     const unsigned a_soff1 = (unsigned)((k1 * p.C + ld_c0) * 4), a_soff2 = (unsigned)((k2 * p.C + ld_c0) * 4);
     const unsigned b_soff = (unsigned)((ld_xi * p.u_gs + ld_c0) * 4);
 #pragma unroll

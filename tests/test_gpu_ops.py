@@ -107,6 +107,47 @@ def test_conv_alpha_silu_bias():
     assert_close(nchw(got), ref, 2e-5, 2e-5, 'alpha/silu')
 
 
+@pytest.mark.parametrize('act', ['none', 'relu', 'silu', 'leaky'])
+@pytest.mark.parametrize('N', [38, 200])
+def test_scalar_and_ragged_vector_store_paths_with_every_finish(N, act, monkeypatch):
+    """The two store paths of the forward epilogue (csrc/igemm_device.h) on a 2 x 9 x 11 map, 64 -> N, 1x1: N = 38 takes the scalar path (N is
+    no multiple of 4), N = 200 the 16-byte path with a ragged last 128-wide tile.  Every activation, with and without the producer mask, with
+    the shift per channel and per row, under alpha, scale and residual -- against float64.  The 16-byte path is also run under
+    NBM_H16=0: with K = 64 (two K-steps) the plan takes the single-stage form under either setting, so the comparison with the default run
+    only states that the switch does not reach short K; the half-step kernel against the two-stage one is
+    test_half_step_kernel_gives_the_bits_of_the_two_stage_kernel."""
+    B, H, W, K = 2, 9, 11, 64
+    M = B * H * W
+    key = (N, act)
+    x = rnd(('ex', key), M, K).double()
+    w = rnd(('ew', key), N, K, scale=(2.0 / K) ** 0.5)
+    sc, sh_n, sh_m = 1 + 0.1 * rnd(('es', key), N), 0.1 * rnd(('eb', key), N), 0.1 * rnd(('er', key), M)
+    res, mask = rnd(('eq', key), M, N), rnd(('em', key), M, N)
+    alpha = 0.75
+    lin = (x @ w.double().t()) * alpha * sc.double()
+    fn = {'relu': F.relu, 'silu': F.silu, 'leaky': lambda t: F.leaky_relu(t, 0.01), 'none': lambda t: t}[act]
+    code = {'relu': ops.ACT_RELU, 'silu': ops.ACT_SILU, 'leaky': ops.ACT_LEAKY, 'none': ops.ACT_NONE}[act]
+    xd, wd, rd, md = dev(x.float()), dev(w), dev(res), dev(mask)
+    for per_row in (False, True):
+        for with_mask in (False, True):
+            ref = fn(lin + (sh_m.double()[:, None] if per_row else sh_n.double()[None, :]) + res.double())
+            if with_mask:
+                ref = ref * (mask > 0)
+
+            def run():
+                y = torch.full((B, H, W, N), float('nan'), device='cuda')
+                ops.gemm_conv(xd, wd, y, B=B, H=H, W=W, Cin=K, N=N, scale=dev(sc), shift=dev(sh_m if per_row else sh_n),
+                              shift_per_row=per_row, residual=rd, alpha=alpha, act=code, mask=md if with_mask else None)
+                return y.view(M, N)
+            got = run()
+            assert_close(got, ref, 2e-5, 2e-5, f'N {N} {act} per_row {per_row} mask {with_mask}')
+            if N % 4 == 0:
+                monkeypatch.setenv('NBM_H16', '0')
+                other = run()
+                monkeypatch.delenv('NBM_H16')
+                assert torch.equal(got, other), (N, act, per_row, with_mask)
+
+
 def test_bgemm_and_row_shift():
     a = rnd('ga', 3, 70, 96)
     b = rnd('gb', 3, 150, 96)
