@@ -60,6 +60,11 @@ class RoiDesc(C.Structure):
                 ('pool', C.c_void_p), ('pe', C.c_void_p), ('level', C.c_void_p)]
 
 
+class RoiHwDesc(C.Structure):
+    """struct nbm_roi_hw_desc (include/nbm_hip.h)."""
+    _fields_ = RoiDesc._fields_ + [('pool_h', C.c_int), ('pool_w', C.c_int)]
+
+
 class AugmentParams(C.Structure):
     """struct nbm_augment_params (include/nbm_hip.h)."""
     _fields_ = [('gain', C.c_float), ('coef', C.c_float), ('denom', C.c_float), ('neg_coef', C.c_float),
@@ -130,6 +135,7 @@ SIGNATURES = {
     'nbm_nms_big_workspace': [_I, _I, C.POINTER(C.c_int64)],
     'nbm_nms_big': [_P, _P, _P, _I, _I, _F, _I, _P, _L, _P, _P, _P, _P, _P],
     'nbm_roi_pool': [C.POINTER(RoiDesc), _P],
+    'nbm_roi_pool_hw': [C.POINTER(RoiHwDesc), _P],
     'nbm_rcnn_post': [_P, _P, _I, _I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P],
     # ---- per-file merge (run_detection.merge_images)
     'nbm_merge_collect': [_P, _P, _I, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P],
@@ -196,6 +202,7 @@ SIGNATURES = {
     'nbm_bn_train_fwd': [_P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P],
     'nbm_bn_train_bwd': [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     'nbm_roi_pool_bwd': [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _P, _P, _I, _I, _P, _P],
+    'nbm_roi_pool_hw_bwd': [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     'nbm_sqnorm_accum': [_P, _L, _P, _P],
     'nbm_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _F, _P],
 }

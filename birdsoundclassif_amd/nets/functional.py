@@ -1010,6 +1010,38 @@ class RoiPool(Function):
         return (None, None, None, None, None, None, *gf)
 
 
+class RoiPoolHW(Function):
+    """ROIPooling at any `--roi_pool_h` x `--roi_pool_w` (ops.roi_pool_plan: 'general') on dense FPN maps: `RoiPool` with the
+    pool size in front and no persistent gradient maps.  Parked RPN shares (_PARKED) and the shared scatter maps (_GRAD_ACC)
+    are honoured as there."""
+
+    @staticmethod
+    def forward(ctx, ph, pw, rois, n_roi, pe_f, pe_t, img_h, img_w, *fmaps):
+        if any(ondemand.lazy_state(f) is not None for f in fmaps):
+            raise NotImplementedError('RoiPoolHW reads dense FPN maps: the demand-driven maps serve the 2 x 2 pool only')
+        pool, pe, level = ops.roi_pool(list(fmaps), rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=(ph, pw), force_general=True)
+        ctx.shapes = [tuple(f.shape) for f in fmaps]
+        ctx.fm_ptrs = [f.data_ptr() for f in fmaps]
+        _GRAD_ACC.clear()                      # nothing of an earlier step may survive into this one's backward pass
+        ctx.save_for_backward(rois, level)
+        ctx.mark_non_differentiable(pe, level)
+        return pool, pe, level
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gpool, _gpe, _glvl):
+        rois, level = ctx.saved_tensors
+        bases = {i: _PARKED.pop(ptr) for i, ptr in enumerate(ctx.fm_ptrs) if ptr in _PARKED}
+        gf = ops.roi_pool_bwd(gpool.contiguous(), rois, level, ctx.shapes, bases={i: (g, e) for i, (g, _, e) in bases.items()},
+                              force_general=True)
+        _GRAD_ACC.clear()
+        if GRAD_SHARE:
+            for i, (ptr, g) in enumerate(zip(ctx.fm_ptrs, gf)):
+                if i not in bases:
+                    _GRAD_ACC[ptr] = weakref.ref(g)
+        return (None, None, None, None, None, None, None, None, *gf)
+
+
 def attention_context(x, wq, bq, wk, bk, wv, bv, inv):
     """x [B, L, C] -> (qkv [B*L, 2d + dv], p [B, L, L] softmaxed, ctx [B*L, dv], wqkv): self_attention.py:40-50 up to (not including)
     the final projection.  dv = rows of wv (= d in the module; the evaluation path passes value weights composed with what follows)."""

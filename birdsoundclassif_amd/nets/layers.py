@@ -215,11 +215,13 @@ class ROIPooling(nn.Module):
         return self._pe[key]
 
     def forward_device(self, rois, n_roi, fmaps_nhwc):
-        """rois [B,cap,4], n_roi device int32 [B] -> pool, pe NHWC [B*cap,2,2,C], level int32 [B,cap]."""
+        """rois [B,cap,4], n_roi device int32 [B] -> pool, pe NHWC [B*cap,ph,pw,C], level int32 [B,cap]
+        (ph x pw = --roi_pool_h x --roi_pool_w; other than 2 x 2: the general kernels, on dense maps)."""
         cfg = self.config
-        if (cfg.roi_pool_h, cfg.roi_pool_w) != (2, 2):
-            raise NotImplementedError('roi_pool 2x2 (reference default) only')
         pe_f, pe_t = self.pe_tables(rois.device)
+        if ops.roi_pool_plan(cfg.roi_pool_h, cfg.roi_pool_w, [tuple(f.shape[1:3]) for f in fmaps_nhwc]) == 'general':
+            return Fn.RoiPoolHW.apply(cfg.roi_pool_h, cfg.roi_pool_w, rois, n_roi, pe_f, pe_t, cfg.img_height, cfg.img_width,
+                                      *fmaps_nhwc)
         for lvl, fm in enumerate(fmaps_nhwc):        # demand-driven maps: compute the tiles under these RoIs first
             if ondemand.lazy_pending(fm):
                 with torch.no_grad():
@@ -230,8 +232,8 @@ class ROIPooling(nn.Module):
         B, R = rois.shape[:2]
         n = torch.full((B,), R, device=rois.device, dtype=torch.int32)
         pool, pe, lvl = self.forward_device(rois.contiguous(), n, [_nhwc(f) for f in conv_out])
-        C_ = pool.shape[-1]
-        return (pool.view(B, R, 2, 2, C_).permute(0, 1, 4, 2, 3), pe.view(B, R, 2, 2, C_).permute(0, 1, 4, 2, 3),
+        ph, pw, C_ = pool.shape[1:]
+        return (pool.view(B, R, ph, pw, C_).permute(0, 1, 4, 2, 3), pe.view(B, R, ph, pw, C_).permute(0, 1, 4, 2, 3),
                 lvl.cpu().numpy())
 
 
@@ -259,8 +261,8 @@ class RCNN(nn.Module):
         return _prep._cached(lin.weight, 'hwc', make)
 
     def forward_nhwc(self, pool, pe):
-        """pool, pe: NHWC [N,2,2,C] -> (bbox_reg [N, 4(1+nc)], bbox_classes [N, 1+nc] softmaxed)."""
-        cn = pool.shape[-1]
+        """pool, pe: NHWC [N,ph,pw,C] -> (bbox_reg [N, 4(1+nc)], bbox_classes [N, 1+nc] softmaxed)."""
+        cn, nbin = pool.shape[-1], pool.shape[1] * pool.shape[2]
         if torch.is_grad_enabled() and (self.training or pool.requires_grad):
             if not self.training:
                 raise NotImplementedError('gradients through the eval-mode (running-statistics) head are not implemented')
@@ -270,8 +272,8 @@ class RCNN(nn.Module):
             for blk in self.rcnn:
                 out = blk(out, pe_act)
             feat = out.reshape(out.shape[0], -1)
-            wr = self.bbox_reg_layer.weight.view(-1, cn, 4).permute(0, 2, 1).reshape(-1, 4 * cn)
-            wc = self.bbox_classif_layer.weight.view(-1, cn, 4).permute(0, 2, 1).reshape(-1, 4 * cn)
+            wr = self.bbox_reg_layer.weight.view(-1, cn, nbin).permute(0, 2, 1).reshape(-1, nbin * cn)
+            wc = self.bbox_classif_layer.weight.view(-1, cn, nbin).permute(0, 2, 1).reshape(-1, nbin * cn)
             reg = Fn.linear(feat, wr, self.bbox_reg_layer.bias)
             cls = Fn.linear(feat, wc, self.bbox_classif_layer.bias)
             return reg, Fn.SoftmaxRows.apply(cls)
@@ -286,7 +288,7 @@ class RCNN(nn.Module):
         return reg, ops.softmax_rows_(cls)
 
     def forward(self, roi_pool_out, roi_pe_out):
-        """[B,R,C,2,2] x2 -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc])."""
+        """[B,R,C,ph,pw] x2 -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc])."""
         p = roi_pool_out.flatten(end_dim=1).permute(0, 2, 3, 1).contiguous()
         e = roi_pe_out.flatten(end_dim=1).permute(0, 2, 3, 1).contiguous()
         return self.forward_nhwc(p, e)
@@ -341,7 +343,7 @@ class Transformer_RCNN(nn.Module):
                 nn.init.xavier_uniform_(p)
 
     def forward_nhwc(self, pool, pe, B, R, n_valid=None, segments=None):
-        """pool, pe: NHWC [B*R,2,2,C]; n_valid: device int32, element 0 = RoIs per image that are real
+        """pool, pe: NHWC [B*R,ph,pw,C]; n_valid: device int32, element 0 = RoIs per image that are real
         (the same count for every image of one model call; pe_qk masks the rest)
         -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc] softmaxed).
         `segments` (int32 [2, B] device table, evaluation only): the batch is one model call per segment and `n_valid` holds
@@ -389,7 +391,8 @@ class Transformer_RCNN(nn.Module):
         """Same computation on the differentiable operator layer (`functional`): every forward and backward step is a
         HIP kernel; torch.autograd only sequences them."""
         cn, M, E = pool.shape[-1], B * R, self.config.tf_model_dim
-        hwc = lambda lin: lin.weight.view(-1, cn, 4).permute(0, 2, 1).reshape(-1, 4 * cn)
+        nbin = pool.shape[1] * pool.shape[2]
+        hwc = lambda lin: lin.weight.view(-1, cn, nbin).permute(0, 2, 1).reshape(-1, nbin * cn)
         pos = Fn.linear(pe.reshape(M, -1), hwc(self.pos_embedding[0]), self.pos_embedding[0].bias, act=Fn.ACT_LEAKY)
         x = Fn.linear(pool.reshape(M, -1), hwc(self.rois_embedding[0]), self.rois_embedding[0].bias, act=Fn.ACT_LEAKY)
         if self.tf_pe_qk:
@@ -416,7 +419,7 @@ class Transformer_RCNN(nn.Module):
         return reg, Fn.SoftmaxRows.apply(cls)
 
     def forward(self, rois, pos):
-        """[B,R,C,2,2] x2 -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc])."""
+        """[B,R,C,ph,pw] x2 -> (bbox_reg [B*R, 4(1+nc)], bbox_classes [B*R, 1+nc])."""
         B, R = rois.shape[:2]
         p = rois.flatten(end_dim=1).permute(0, 2, 3, 1).contiguous()
         e = pos.flatten(end_dim=1).permute(0, 2, 3, 1).contiguous()

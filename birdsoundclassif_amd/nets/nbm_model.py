@@ -36,8 +36,11 @@ class NbmModel(nn.Module):
         Level 0 (stride 8): three 2x2 tiles out of four are never read.  Level 1 (stride 4): every tile holds a pattern pixel, so
         the listed F(2x2,3x3) tiles gained nothing there (round 2: 10.1 -> 8.5 ms at B = 64, eaten by the RoI phase); with the
         pattern pixels going through the cell transforms (csrc/cellwino.hip: 25 plane products per 4x4 cell instead of the 64 of
-        its four tiles) it pays: detect step 81.4 -> 75.6 ms at B = 64."""
+        its four tiles) it pays: detect step 81.4 -> 75.6 ms at B = 64.
+        A RoI pool other than 2 x 2 reads dense maps (the tile lists and the footprint re-zeroing know the 2 x 2 windows only)."""
         a = self.args
+        if (getattr(a, 'roi_pool_h', 2), getattr(a, 'roi_pool_w', 2)) != (2, 2):
+            return None
         if getattr(a, 'fpn_first', False) or getattr(a, 'sandwich_attn', False) or getattr(a, 'fpn', 'fpn') != 'fpn':
             return None
         st = a.anchor_stride / 2

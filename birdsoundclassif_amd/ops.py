@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import GconvBwdDesc, GconvDesc, GemmDesc, RoiDesc, check
+from ._lib import GconvBwdDesc, GconvDesc, GemmDesc, RoiDesc, RoiHwDesc, check
 
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_LEAKY = 0, 1, 2, 3
 
@@ -965,13 +965,32 @@ def nms_batched(boxes, scores, n_in, thresh, post_n, segments=None, force_big=Fa
     return rois, rs, n_out
 
 
-def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w):
+def roi_pool_plan(ph, pw, fmap_hw):
+    """Which RoI-pooling kernels serve a `--roi_pool_h` x `--roi_pool_w` pool on maps of the sizes `fmap_hw` [(h, w), ...]
+    -> 'fixed2x2' (nbm_roi_pool / nbm_roi_pool_bwd, the reference's default) or 'general' (nbm_roi_pool_hw / _bwd, dense
+    maps only).  Host-only; refuses the two pool sizes the reference itself cannot run."""
+    ph, pw = int(ph), int(pw)
+    if ph < 2 or pw < 2:
+        raise ValueError(f'--roi_pool_h {ph} / --roi_pool_w {pw}: a pool below 2 x 2 is no configuration of the reference -- its '
+                         'positional-encoding slice pe_frequency[s*y1 : s*y2] is empty for a one-row window (layers.py:484), '
+                         'and the average of an empty slice is NaN')
+    mh, mw = min(int(h) for h, _ in fmap_hw), min(int(w) for _, w in fmap_hw)
+    if ph > mh or pw > mw:
+        raise ValueError(f'--roi_pool_h {ph} / --roi_pool_w {pw} exceeds the smallest pyramid map ({mh} x {mw}): the '
+                         "reference's growth loop (layers.py:459-465) does not terminate when a window cannot reach the pool size")
+    return 'fixed2x2' if (ph, pw) == (2, 2) else 'general'
+
+
+def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=(2, 2), force_general=False):
     """fmaps: list of NHWC [B,h,w,C]; rois [B,cap,4]; n_roi device int32 [B] (or [1], `roi_counts`) -> pool,
-    pe [B*cap,2,2,C], level [B,cap]."""
+    pe [B*cap,ph,pw,C], level [B,cap].  `pool_hw` other than (2, 2) runs nbm_roi_pool_hw (dense maps); `force_general` sends
+    2 x 2 there too (tests: its outputs are the bits of nbm_roi_pool)."""
     B, cap = rois.shape[:2]
+    ph, pw = int(pool_hw[0]), int(pool_hw[1])
+    general = roi_pool_plan(ph, pw, [tuple(f.shape[1:3]) for f in fmaps]) == 'general' or force_general
     n_roi = roi_counts(n_roi, B)
     C_ = fmaps[0].shape[-1]
-    d = RoiDesc()
+    d = RoiHwDesc() if general else RoiDesc()
     for i, f in enumerate(fmaps):
         _chk(f, name=f'fmap{i}')
         d.fmap[i] = f.data_ptr()
@@ -979,11 +998,15 @@ def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w):
     d.n_levels, d.C = len(fmaps), C_
     d.rois, d.n_roi, d.B, d.roi_cap = _chk(rois).data_ptr(), n_roi.data_ptr(), B, cap
     d.pe_f, d.pe_t, d.img_h, d.img_w = _chk(pe_f).data_ptr(), _chk(pe_t).data_ptr(), img_h, img_w
-    pool = torch.zeros((B * cap, 2, 2, C_), device=rois.device, dtype=torch.float32)
-    pe = torch.zeros((B * cap, 2, 2, C_), device=rois.device, dtype=torch.float32)
+    pool = torch.zeros((B * cap, ph, pw, C_), device=rois.device, dtype=torch.float32)
+    pe = torch.zeros((B * cap, ph, pw, C_), device=rois.device, dtype=torch.float32)
     level = torch.zeros((B, cap), device=rois.device, dtype=torch.int32)
     d.pool, d.pe, d.level = pool.data_ptr(), pe.data_ptr(), level.data_ptr()
-    check(lib().nbm_roi_pool(C.byref(d), _stream()), 'nbm_roi_pool')
+    if general:
+        d.pool_h, d.pool_w = ph, pw
+        check(lib().nbm_roi_pool_hw(C.byref(d), _stream()), 'nbm_roi_pool_hw')
+    else:
+        check(lib().nbm_roi_pool(C.byref(d), _stream()), 'nbm_roi_pool')
     return pool, pe, level
 
 
@@ -1519,12 +1542,17 @@ def bn_train_bwd(g2d, x2d, mean, invstd, w):
     return gx, gw, gb
 
 
-def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None):
-    """gpool [B*R,2,2,C] -> list of zero-initialised-then-accumulated gradient maps (NHWC) for the FPN levels.
+def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None, force_general=False):
+    """gpool [B*R,ph,pw,C] -> list of zero-initialised-then-accumulated gradient maps (NHWC) for the FPN levels.
     `pooled` {level index: stride of the RPN's depthwise convolution on that map}: those maps come from the persistent pool of
-    `ondemand.zero_acquire` (demand-driven levels: the consumer of the gradient recycles them) instead of a fresh fill."""
+    `ondemand.zero_acquire` (demand-driven levels: the consumer of the gradient recycles them) instead of a fresh fill.
+    The pool size is gpool's; other than 2 x 2 (or `force_general`) runs nbm_roi_pool_hw_bwd, on dense maps only: the
+    footprint re-zeroing of the persistent maps knows the 2 x 2 windows alone."""
     B, R = rois.shape[:2]
-    C_ = gpool.shape[-1]
+    ph, pw, C_ = gpool.shape[1:]
+    general = roi_pool_plan(ph, pw, [s[1:3] for s in fmap_shapes]) == 'general' or force_general
+    if general and (pooled or any(e is not None for _, e in (bases or {}).values())):
+        raise NotImplementedError('roi_pool_bwd: persistent (demand-driven) gradient maps exist for the 2 x 2 pool only')
     gf = []
     for i, s in enumerate(fmap_shapes):
         buf = None
@@ -1556,6 +1584,10 @@ def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None):
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in gf])
     fh = (C.c_int * n)(*[s[1] for s in fmap_shapes])
     fw = (C.c_int * n)(*[s[2] for s in fmap_shapes])
+    if general:
+        check(lib().nbm_roi_pool_hw_bwd(ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, ph, pw, _ptr(_chk(gpool)),
+                                        _stream()), 'nbm_roi_pool_hw_bwd')
+        return gf
     check(lib().nbm_roi_pool_bwd(ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, _ptr(_chk(gpool)), _stream()),
           'nbm_roi_pool_bwd')
     return gf

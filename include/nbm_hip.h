@@ -569,6 +569,30 @@ typedef struct nbm_roi_desc {
 } nbm_roi_desc;
 int nbm_roi_pool(const nbm_roi_desc* d, void* stream);
 
+/* ROIPooling (layers.py:406-497) at any pool size (train.py:115-117, --roi_pool_h / --roi_pool_w): the fields of nbm_roi_desc
+ * plus pool_h, pool_w.  Level assignment, rounding, the y2 clamp and the clamped x2 for the map / unclamped x2 for the encoding
+ * are those of nbm_roi_pool; the window is grown to at least pool_h x pool_w (layers.py:459-465, as a loop bounded by the pool
+ * size), bins are [floor(i*h/ph), ceil((i+1)*h/ph)) x [floor(j*w/pw), ceil((j+1)*w/pw)), each summed row-major in fp32 and
+ * divided once by its area; the positional encoding is accumulated in double and rounded once.  pool_h = pool_w = 2 gives the
+ * bits of nbm_roi_pool.  The maps are dense.  One workgroup per RoI slot, 16-byte accesses along C when C % 4 == 0 and the map
+ * and output pointers are 16-byte aligned, 4-byte accesses otherwise.  Slots r >= n_roi[b] are left untouched.
+ * Outputs NHWC [B*roi_cap][pool_h][pool_w][C].
+ * Refused before any launch, nothing written: NBM_EUNSUPPORTED for pool_h < 2 or pool_w < 2 (the reference's one-row
+ * positional-encoding slice layers.py:484 is empty, its mean NaN) and for pool_h > min(fh) or pool_w > min(fw) (the reference's
+ * growth loop does not terminate); NBM_EINVAL for n_levels outside 1..5, odd C, null pointers. */
+typedef struct nbm_roi_hw_desc {
+  const float* fmap[5];
+  int fh[5], fw[5];
+  int n_levels, C;
+  const float* rois;     /* [B][roi_cap][4] */
+  const int* n_roi;      /* device int32 [B] */
+  int B, roi_cap;
+  const float* pe_f; const float* pe_t; int img_h, img_w;
+  float* pool; float* pe; int* level;
+  int pool_h, pool_w;
+} nbm_roi_hw_desc;
+int nbm_roi_pool_hw(const nbm_roi_hw_desc* d, void* stream);
+
 /* FastRCNN eval post-processing (layers.py:688-776) for B images, n_roi[b] RoIs in image b:
  * class arg-max, per-class delta gather, decode+clip, sort by score, drop background, class-agnostic
  * NMS, per-class NMS (top proposal_number) and score > min_score.  Output rows sorted by (class asc,
@@ -766,6 +790,13 @@ int nbm_bn_train_bwd(const float* g, const float* x, int64_t M, int C, const flo
 /* ROIPooling backward: scatter-add of gpool [B*n_roi][2][2][C] into the (zeroed) FPN gradient maps */
 int nbm_roi_pool_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
                      const float* rois, const int* level, int B, int n_roi, const float* gpool, void* stream);
+/* ROIPooling backward at any pool size (autograd of layers.py:406-497 with --roi_pool_h / --roi_pool_w): scatter-add of
+ * gpool [B*n_roi][pool_h][pool_w][C] into the given gradient maps, windows and bins of nbm_roi_pool_hw on the levels in
+ * `level`.  The sums are fp32 atomics: RoI windows overlap, so their order -- and the last bits of the result -- is not fixed.
+ * Argument checks as nbm_roi_pool_hw. */
+int nbm_roi_pool_hw_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
+                        const float* rois, const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
+                        void* stream);
 /* out[0] += sum g^2 (double); then AdamW on a flat range with the clip coefficient min(1, max_norm/(sqrt(*sqnorm)+1e-6))
  * evaluated on device (sqnorm NULL or max_norm <= 0: no clipping). */
 int nbm_sqnorm_accum(const float* g, int64_t n, double* out, void* stream);
