@@ -908,64 +908,9 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ g, const float* __
   }
 }
 
-// ---- RoI pooling gradient (scatter with atomics; RoI windows overlap)
-struct RoiBwdParams {
-  float* gfmap[5]; int fh[5], fw[5]; int C; const float* rois; const int* level; int B, n_roi; const float* gpool;
-};
-__global__ void roi_pool_bwd_kernel(const RoiBwdParams p) {
-  const int slot = blockIdx.x;
-  const int b = slot / p.n_roi;
-  const float* roi = p.rois + (long long)slot * 4;
-  const int lvl = p.level[slot];
-  const float stride = (float)(2 << lvl);
-  int x1 = (int)rintf(roi[0] / stride), y1 = (int)rintf(roi[1] / stride);
-  int x2 = (int)rintf(roi[2] / stride), y2 = (int)rintf(roi[3] / stride);
-  const int H = p.fh[lvl], W = p.fw[lvl];
-  y2 = min(y2, H - 1);
-  while (y2 - y1 + 1 < 2) { y1 = max(0, y1 - 1); y2 = min(H - 1, y2 + 1); }
-  while (x2 - x1 + 1 < 2) { x1 = max(0, x1 - 1); x2 = min(W - 1, x2 + 1); }
-  const int h = y2 - y1 + 1, w = min(x2, W - 1) - x1 + 1;
-  float* gf = p.gfmap[lvl];
-  const int C = p.C;
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int ya = (i * h) / 2, yb = ((i + 1) * h + 1) / 2;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int xa = (j * w) / 2, xb = ((j + 1) * w + 1) / 2;
-        const float gv = p.gpool[((long long)slot * 4 + i * 2 + j) * C + c] / (float)((yb - ya) * (xb - xa));
-        for (int yy = ya; yy < yb; ++yy)
-          for (int xx = xa; xx < xb; ++xx)
-            atomicAdd(gf + (((long long)b * H + y1 + yy) * W + x1 + xx) * C + c, gv);
-      }
-    }
-  }
-}
-
 // ---- targeted re-zeroing of the persistent gradient maps of a demand-driven FPN level (nbm_hip.h: nbm_zero_*): the map is zero
-// everywhere except where these three writers left something, so restoring it costs their footprint, not a fill of the whole map.
-__global__ void zero_roi_windows_kernel(float* __restrict__ g, int H, int W, int C4, const float* __restrict__ rois,
-                                        const int* __restrict__ level, int n_roi, int lvl) {
-  const int slot = blockIdx.x;
-  if (level[slot] != lvl) return;
-  const int b = slot / n_roi;
-  const float* roi = rois + (long long)slot * 4;
-  const float stride = (float)(2 << lvl);
-  int x1 = (int)rintf(roi[0] / stride), y1 = (int)rintf(roi[1] / stride);           // the window of roi_pool_bwd_kernel
-  int x2 = (int)rintf(roi[2] / stride), y2 = (int)rintf(roi[3] / stride);
-  y2 = min(y2, H - 1);
-  while (y2 - y1 + 1 < 2) { y1 = max(0, y1 - 1); y2 = min(H - 1, y2 + 1); }
-  while (x2 - x1 + 1 < 2) { x1 = max(0, x1 - 1); x2 = min(W - 1, x2 + 1); }
-  const int h = y2 - y1 + 1, w = min(x2, W - 1) - x1 + 1;
-  f32x4* g4 = reinterpret_cast<f32x4*>(g);
-  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < h * w * C4; i += blockDim.x) {
-    const int c = i % C4, px = i / C4;
-    const int yy = px / w, xx = px - yy * w;
-    g4[(((long long)b * H + y1 + yy) * W + x1 + xx) * C4 + c] = z;
-  }
-}
+// everywhere except where three writers left something, so restoring it costs their footprint, not a fill of the whole map
+// (the RoI windows: roipool.hip, which owns the window).
 __global__ void zero_pattern_kernel(float* __restrict__ g, int H, int W, int C4, int stride, int OH, int OW) {
   const int cell = blockIdx.x, b = blockIdx.y;
   const int oy = cell / OW, ox = cell - oy * OW;
@@ -1321,22 +1266,6 @@ extern "C" int nbm_bn_train_bwd(const float* g, const float* x, int64_t M, int C
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(256), 0, ST, g, x, (long long)M, C, mean, invstd, red_ws);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * C)), dim3(TPB), 0, ST, g, x, (long long)M, C, mean, invstd, w,
                      red_ws, gx, gw, gb);
-  return nbm_launch_status();
-}
-extern "C" int nbm_roi_pool_bwd(float* const* gfmap, const int* fh, const int* fw, int n_levels, int C, const float* rois,
-                                const int* level, int B, int n_roi, const float* gpool, void* stream) {
-  if (!gfmap || !fh || !fw || !rois || !level || !gpool || n_levels < 1 || n_levels > 5 || B <= 0 || n_roi <= 0) return NBM_EINVAL;
-  RoiBwdParams p;
-  for (int i = 0; i < 5; ++i) { p.gfmap[i] = i < n_levels ? gfmap[i] : nullptr; p.fh[i] = i < n_levels ? fh[i] : 0; p.fw[i] = i < n_levels ? fw[i] : 0; }
-  p.C = C; p.rois = rois; p.level = level; p.B = B; p.n_roi = n_roi; p.gpool = gpool;
-  hipLaunchKernelGGL(roi_pool_bwd_kernel, dim3(B * n_roi), dim3(256), 0, ST, p);
-  return nbm_launch_status();
-}
-extern "C" int nbm_zero_roi_windows(float* g, int H, int W, int C, const float* rois, const int* level, int B, int n_roi, int lvl,
-                                    void* stream) {
-  if (!g || !rois || !level || B <= 0 || n_roi <= 0 || H < 2 || W < 2 || C <= 0 || (C & 3) || lvl < 0 || lvl > 4) return NBM_EINVAL;
-  if (!nbm_aligned16(g)) return NBM_EALIGN;
-  hipLaunchKernelGGL(zero_roi_windows_kernel, dim3(B * n_roi), dim3(256), 0, ST, g, H, W, C / 4, rois, level, n_roi, lvl);
   return nbm_launch_status();
 }
 extern "C" int nbm_zero_pattern(float* g, int B, int H, int W, int C, int stride, void* stream) {

@@ -1,8 +1,11 @@
-// RoI pooling at any pool size (--roi_pool_h / --roi_pool_w): nbm_roi_pool_hw / nbm_roi_pool_hw_bwd (include/nbm_hip.h).
-// The 2 x 2 default keeps its own kernels (detect.hip: roi_pool_kernel, pointwise_bwd.hip: roi_pool_bwd_kernel); these read and
-// write dense FPN maps only.  With pool_h = pool_w = 2 every operation below is the one roi_pool_kernel performs, in its order,
-// so the outputs are its bits.
+// Everything that depends on the RoI window (include/nbm_hip.h): RoI pooling at any pool size and its gradient
+// (nbm_roi_pool_hw / nbm_roi_pool_hw_bwd; nbm_roi_pool / nbm_roi_pool_bwd forward to them with a 2 x 2 pool), the tile lists
+// under the 2 x 2 windows of a demand-driven level (nbm_roi_tiles) and the re-zeroing of those windows in a persistent
+// gradient map (nbm_zero_roi_windows).  roi_level and roi_window below are the only statement of the window: the tile lists,
+// the footprint re-zeroing and the pooling agree because they call them.
 #include "nbm_common.h"
+#include <cstddef>
+#include <cstring>
 
 namespace {
 
@@ -20,7 +23,7 @@ struct RoiHwBwdParams {
   int ph, pw;
 };
 
-// Pyramid level of a RoI, layers.py:408-417 (sizes WITHOUT the +1): roi_window of detect.hip.
+// Pyramid level of a RoI, layers.py:408-417 (sizes WITHOUT the +1).
 __device__ __forceinline__ int roi_level(const float* roi, int n_levels) {
   const float size = sqrtf((roi[2] - roi[0]) * (roi[3] - roi[1]));
   const float lf = logf(size * 0.1f) / 0.6931471805599453f;
@@ -34,8 +37,8 @@ __device__ __forceinline__ int roi_level(const float* roi, int n_levels) {
 // width >= 1 and gains at least one row / column per round from the second round on, so the bound is never what ends it.
 // Rows read: y1..y2, columns: x1..min(x2, W-1); x2 itself stays unclamped for the positional encoding.
 // -> false for a window with no pixel in the map (coordinates outside the image: nothing is read or written for it).
-__device__ __forceinline__ bool roi_window_hw(const float* roi, int lvl, int H, int W, int ph, int pw, int& x1, int& y1, int& x2,
-                                              int& y2) {
+__device__ __forceinline__ bool roi_window(const float* roi, int lvl, int H, int W, int ph, int pw, int& x1, int& y1, int& x2,
+                                           int& y2) {
   const float stride = (float)(2 << lvl);
   x1 = (int)rintf(roi[0] / stride); y1 = (int)rintf(roi[1] / stride);
   x2 = (int)rintf(roi[2] / stride); y2 = (int)rintf(roi[3] / stride);
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(256) void roi_pool_hw_kernel(const RoiHwParams p) {
   const int lvl = roi_level(roi, p.n_levels);
   const int H = p.fh[lvl], W = p.fw[lvl], ph = p.ph, pw = p.pw;
   int x1, y1, x2, y2;
-  const bool inside = roi_window_hw(roi, lvl, H, W, ph, pw, x1, y1, x2, y2);
+  const bool inside = roi_window(roi, lvl, H, W, ph, pw, x1, y1, x2, y2);
   if (threadIdx.x == 0) p.level[slot] = lvl;
   if (!inside) return;
   const int C = p.C, half = C >> 1, nbin = ph * pw;
@@ -126,13 +129,13 @@ __global__ __launch_bounds__(256) void roi_pool_hw_bwd_kernel(const RoiHwBwdPara
   const int lvl = min(max(p.level[slot], 0), p.n_levels - 1);
   const int H = p.fh[lvl], W = p.fw[lvl], ph = p.ph, pw = p.pw;
   int x1, y1, x2, y2;
-  if (!roi_window_hw(roi, lvl, H, W, ph, pw, x1, y1, x2, y2)) return;
+  if (!roi_window(roi, lvl, H, W, ph, pw, x1, y1, x2, y2)) return;
   const int C = p.C, nbin = ph * pw;
   float* gf = p.gfmap[lvl] + ((long long)b * H + y1) * W * C + (long long)x1 * C;
   const float* g = p.gpool + (long long)slot * nbin * C;
   const int h = y2 - y1 + 1, w = min(x2, W - 1) - x1 + 1;
-  // work items are (bin, channel): neighbouring lanes add to neighbouring floats, as in roi_pool_bwd_kernel (a lane per channel
-  // quad spreads each atomic instruction over four times the cache lines: 4.2 x slower at 2 x 2, measured)
+  // work items are (bin, channel): neighbouring lanes add to neighbouring floats (a lane per channel quad spreads each atomic
+  // instruction over four times the cache lines: 4.2 x slower at 2 x 2, measured)
   for (int it = threadIdx.x; it < nbin * C; it += blockDim.x) {
     const int bin = it / C, c = it - bin * C;
     const int i = bin / pw, j = bin - i * pw;
@@ -141,6 +144,93 @@ __global__ __launch_bounds__(256) void roi_pool_hw_bwd_kernel(const RoiHwBwdPara
     const float gv = g[(long long)bin * C + c] / (float)((yb - ya) * (xb - xa));
     for (int yy = ya; yy < yb; ++yy)
       for (int xx = xa; xx < xb; ++xx) atomicAdd(gf + ((long long)yy * W + xx) * C + c, gv);
+  }
+}
+
+// ------------------------------------------------------------------ demand-driven pyramid level: tiles under the RoIs
+// The finest FPN output map is read by two consumers only: the RPN's stride-8 depthwise convolution (a fixed pixel pattern)
+// and the RoI pooling of the RoIs assigned to that level.  This kernel lists the 2 x 2 Winograd output tiles of level `level`
+// that the 2 x 2 pool's RoI windows touch (minus the tiles in `skip`, which the fixed pattern has computed already): one
+// workgroup per image, an LDS bitmap, then an ordered compaction into 128-entry blocks (entries = b * TH * TW + ty * TW + tx,
+// ascending, -1 padded, a block never mixes images); blocks are handed out by an atomic counter, so the filled blocks are the
+// leading *n_blocks ones of `tiles` (capacity B * ceil(TH * TW / 128) blocks: cannot overflow).
+struct RoiTilesParams {
+  const float* rois; const int* n_roi; int B, roi_cap, n_levels, level, H, W;
+  const unsigned char* skip; int* tiles; int* n_blocks; int dilate;
+};
+
+__global__ __launch_bounds__(256) void roi_tiles_kernel(const RoiTilesParams p) {
+  extern __shared__ unsigned bits[];
+  __shared__ int part[256];
+  __shared__ int base_s;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int H = p.H, W = p.W;
+  const int TH = (H + 1) >> 1, TW = (W + 1) >> 1, THW = TH * TW;
+  const int n_words = (THW + 31) >> 5;
+  for (int i = tid; i < n_words; i += 256) bits[i] = 0u;
+  __syncthreads();
+  const int n = min(p.n_roi[b], p.roi_cap);
+  for (int r = tid; r < n; r += 256) {
+    const float* roi = p.rois + ((long long)b * p.roi_cap + r) * 4;
+    int x1, y1, x2, y2;
+    if (roi_level(roi, p.n_levels) != p.level || !roi_window(roi, p.level, H, W, 2, 2, x1, y1, x2, y2)) continue;
+    const int dl = p.dilate;           // > 0: the tiles within `dilate` pixels of the window (support of a 3x3 data gradient)
+    const int ty0 = max(y1 - dl, 0) >> 1, ty1 = min(y2 + dl, H - 1) >> 1, tx0 = max(x1 - dl, 0) >> 1, tx1 = min(min(x2, W - 1) + dl, W - 1) >> 1;
+    for (int ty = ty0; ty <= ty1; ++ty)
+      for (int tx = tx0; tx <= tx1; ++tx) {
+        const int id = ty * TW + tx;
+        if (p.skip && p.skip[id]) continue;
+        atomicOr(&bits[id >> 5], 1u << (id & 31));
+      }
+  }
+  __syncthreads();
+  // ordered compaction: thread t owns the words [t * wpt, (t + 1) * wpt)
+  const int wpt = (n_words + 255) / 256;
+  int cnt = 0;
+  for (int i = tid * wpt; i < min((tid + 1) * wpt, n_words); ++i) cnt += __popc(bits[i]);
+  part[tid] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    int run = 0;
+    for (int i = 0; i < 256; ++i) { const int c = part[i]; part[i] = run; run += c; }
+    base_s = run ? atomicAdd(p.n_blocks, (run + 127) >> 7) : 0;
+    part[0] = 0;
+    bits[n_words] = (unsigned)run;                               // total, one spare word
+  }
+  __syncthreads();
+  const int total = (int)bits[n_words];
+  if (!total) return;
+  int* out = p.tiles + (long long)base_s * 128;
+  int o = part[tid];
+  for (int i = tid * wpt; i < min((tid + 1) * wpt, n_words); ++i) {
+    unsigned wbits = bits[i];
+    while (wbits) {
+      const int bit = __ffs(wbits) - 1;
+      wbits &= wbits - 1;
+      out[o++] = b * THW + (i << 5) + bit;
+    }
+  }
+  const int padded = ((total + 127) >> 7) << 7;
+  for (int i = total + tid; i < padded; i += 256) out[i] = -1;
+}
+
+// Targeted re-zeroing of the persistent gradient map of a demand-driven FPN level (nbm_hip.h: nbm_zero_*): the map is zero
+// everywhere except where its writers left something, so restoring it costs their footprint, not a fill of the whole map.
+// This one undoes roi_pool_hw_bwd_kernel's scatter of a 2 x 2 pool on level `lvl`.
+__global__ void zero_roi_windows_kernel(float* __restrict__ g, int H, int W, int C4, const float* __restrict__ rois,
+                                        const int* __restrict__ level, int n_roi, int lvl) {
+  const int slot = blockIdx.x;
+  if (level[slot] != lvl) return;
+  const int b = slot / n_roi;
+  int x1, y1, x2, y2;
+  if (!roi_window(rois + (long long)slot * 4, lvl, H, W, 2, 2, x1, y1, x2, y2)) return;
+  const int h = y2 - y1 + 1, w = min(x2, W - 1) - x1 + 1;
+  f32x4* g4 = reinterpret_cast<f32x4*>(g);
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < h * w * C4; i += blockDim.x) {
+    const int c = i % C4, px = i / C4;
+    const int yy = px / w, xx = px - yy * w;
+    g4[(((long long)b * H + y1 + yy) * W + x1 + xx) * C4 + c] = z;
   }
 }
 
@@ -196,5 +286,53 @@ extern "C" int nbm_roi_pool_hw_bwd(float* const* gfmap, const int* fh, const int
   p.n_levels = n_levels; p.C = C; p.rois = rois; p.level = level; p.B = B; p.n_roi = n_roi; p.gpool = gpool;
   p.ph = pool_h; p.pw = pool_w;
   hipLaunchKernelGGL(roi_pool_hw_bwd_kernel, dim3(B * n_roi), dim3(256), 0, (hipStream_t)stream, p);
+  return nbm_launch_status();
+}
+
+// The 2 x 2 entries of the ABI: the same checks and kernels with the pool size filled in.
+static_assert(offsetof(nbm_roi_hw_desc, pool_h) == sizeof(nbm_roi_desc), "nbm_roi_hw_desc is nbm_roi_desc plus the pool size");
+
+extern "C" int nbm_roi_pool(const nbm_roi_desc* d, void* stream) {
+  if (!d) return NBM_EINVAL;
+  nbm_roi_hw_desc h;
+  memcpy(&h, d, sizeof(*d));
+  h.pool_h = h.pool_w = 2;
+  return nbm_roi_pool_hw(&h, stream);
+}
+
+extern "C" int nbm_roi_pool_bwd(float* const* gfmap, const int* fh, const int* fw, int n_levels, int C, const float* rois,
+                                const int* level, int B, int n_roi, const float* gpool, void* stream) {
+  return nbm_roi_pool_hw_bwd(gfmap, fh, fw, n_levels, C, rois, level, B, n_roi, 2, 2, gpool, stream);
+}
+
+// RoI windows of pyramid level `level` -> list of the 2 x 2 output tiles they touch -- see nbm_hip.h.
+extern "C" int nbm_roi_tiles(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level,
+                             const int* fh, const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks,
+                             void* stream) {
+  if (!rois || !n_roi || !fh || !fw || !tiles || !n_blocks || B <= 0 || roi_cap <= 0 || n_levels < 1 || n_levels > 5 ||
+      level < 0 || level >= n_levels || dilate < 0 || dilate > 2)
+    return NBM_EINVAL;
+  for (int i = 0; i < n_levels; ++i)
+    if (fh[i] < 2 || fw[i] < 2) return NBM_EINVAL;
+  RoiTilesParams p{};
+  p.rois = rois; p.n_roi = n_roi; p.B = B; p.roi_cap = roi_cap; p.n_levels = n_levels; p.level = level;
+  p.H = fh[level]; p.W = fw[level];
+  p.skip = skip; p.tiles = tiles; p.n_blocks = n_blocks; p.dilate = dilate;
+  const int thw = ((p.H + 1) >> 1) * ((p.W + 1) >> 1);
+  const size_t lds = (size_t)(((thw + 31) >> 5) + 1) * 4;
+  if (lds > 60000) return NBM_EUNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = nbm_zero_async(n_blocks, sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(roi_tiles_kernel, dim3(B), dim3(256), lds, st, p);
+  return nbm_launch_status();
+}
+
+extern "C" int nbm_zero_roi_windows(float* g, int H, int W, int C, const float* rois, const int* level, int B, int n_roi, int lvl,
+                                    void* stream) {
+  if (!g || !rois || !level || B <= 0 || n_roi <= 0 || H < 2 || W < 2 || C <= 0 || (C & 3) || lvl < 0 || lvl > 4) return NBM_EINVAL;
+  if (!nbm_aligned16(g)) return NBM_EALIGN;
+  hipLaunchKernelGGL(zero_roi_windows_kernel, dim3(B * n_roi), dim3(256), 0, (hipStream_t)stream, g, H, W, C / 4, rois, level,
+                     n_roi, lvl);
   return nbm_launch_status();
 }

@@ -972,11 +972,15 @@ class SoftmaxRows(Function):
 
 
 class RoiPool(Function):
-    """ROIPooling (reference layers.py:406-497): gradient flows to the five FPN maps only."""
+    """ROIPooling (reference layers.py:406-497) at `ph` x `pw` = `--roi_pool_h` x `--roi_pool_w`: gradient flows to the five FPN
+    maps only.  Demand-driven maps and persistent gradient maps serve the 'ondemand' pool alone (ops.roi_pool_plan)."""
 
     @staticmethod
-    def forward(ctx, rois, n_roi, pe_f, pe_t, img_h, img_w, *fmaps):
-        pool, pe, level = ops.roi_pool(list(fmaps), rois, n_roi, pe_f, pe_t, img_h, img_w)
+    def forward(ctx, ph, pw, rois, n_roi, pe_f, pe_t, img_h, img_w, *fmaps):
+        if ops.roi_pool_plan(ph, pw, [tuple(f.shape[1:3]) for f in fmaps]) == 'dense' and \
+                any(ondemand.lazy_state(f) is not None for f in fmaps):
+            raise NotImplementedError(f'RoiPool {ph} x {pw} reads dense FPN maps: the demand-driven maps serve the 2 x 2 pool only')
+        pool, pe, level = ops.roi_pool(list(fmaps), rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=(ph, pw))
         ctx.shapes = [tuple(f.shape) for f in fmaps]
         ctx.fm_ptrs = [f.data_ptr() for f in fmaps]
         # demand-driven levels whose backward pass goes through the cell transforms: their gradient maps are persistent
@@ -1004,38 +1008,6 @@ class RoiPool(Function):
                               bases={i: (g, e) for i, (g, _, e) in bases.items()})
         _GRAD_ACC.clear()
         if GRAD_SHARE:                         # the other consumer of each map may add its gradient here (Fn.DwConv.backward)
-            for i, (ptr, g) in enumerate(zip(ctx.fm_ptrs, gf)):
-                if i not in bases:
-                    _GRAD_ACC[ptr] = weakref.ref(g)
-        return (None, None, None, None, None, None, *gf)
-
-
-class RoiPoolHW(Function):
-    """ROIPooling at any `--roi_pool_h` x `--roi_pool_w` (ops.roi_pool_plan: 'general') on dense FPN maps: `RoiPool` with the
-    pool size in front and no persistent gradient maps.  Parked RPN shares (_PARKED) and the shared scatter maps (_GRAD_ACC)
-    are honoured as there."""
-
-    @staticmethod
-    def forward(ctx, ph, pw, rois, n_roi, pe_f, pe_t, img_h, img_w, *fmaps):
-        if any(ondemand.lazy_state(f) is not None for f in fmaps):
-            raise NotImplementedError('RoiPoolHW reads dense FPN maps: the demand-driven maps serve the 2 x 2 pool only')
-        pool, pe, level = ops.roi_pool(list(fmaps), rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=(ph, pw), force_general=True)
-        ctx.shapes = [tuple(f.shape) for f in fmaps]
-        ctx.fm_ptrs = [f.data_ptr() for f in fmaps]
-        _GRAD_ACC.clear()                      # nothing of an earlier step may survive into this one's backward pass
-        ctx.save_for_backward(rois, level)
-        ctx.mark_non_differentiable(pe, level)
-        return pool, pe, level
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gpool, _gpe, _glvl):
-        rois, level = ctx.saved_tensors
-        bases = {i: _PARKED.pop(ptr) for i, ptr in enumerate(ctx.fm_ptrs) if ptr in _PARKED}
-        gf = ops.roi_pool_bwd(gpool.contiguous(), rois, level, ctx.shapes, bases={i: (g, e) for i, (g, _, e) in bases.items()},
-                              force_general=True)
-        _GRAD_ACC.clear()
-        if GRAD_SHARE:
             for i, (ptr, g) in enumerate(zip(ctx.fm_ptrs, gf)):
                 if i not in bases:
                     _GRAD_ACC[ptr] = weakref.ref(g)

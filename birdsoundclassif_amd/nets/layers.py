@@ -216,17 +216,14 @@ class ROIPooling(nn.Module):
 
     def forward_device(self, rois, n_roi, fmaps_nhwc):
         """rois [B,cap,4], n_roi device int32 [B] -> pool, pe NHWC [B*cap,ph,pw,C], level int32 [B,cap]
-        (ph x pw = --roi_pool_h x --roi_pool_w; other than 2 x 2: the general kernels, on dense maps)."""
+        (ph x pw = --roi_pool_h x --roi_pool_w; other than 2 x 2 reads dense maps: no map is pending then)."""
         cfg = self.config
         pe_f, pe_t = self.pe_tables(rois.device)
-        if ops.roi_pool_plan(cfg.roi_pool_h, cfg.roi_pool_w, [tuple(f.shape[1:3]) for f in fmaps_nhwc]) == 'general':
-            return Fn.RoiPoolHW.apply(cfg.roi_pool_h, cfg.roi_pool_w, rois, n_roi, pe_f, pe_t, cfg.img_height, cfg.img_width,
-                                      *fmaps_nhwc)
         for lvl, fm in enumerate(fmaps_nhwc):        # demand-driven maps: compute the tiles under these RoIs first
             if ondemand.lazy_pending(fm):
                 with torch.no_grad():
                     ondemand.lazy_complete(fm, rois.detach(), n_roi, [tuple(f.shape[1:3]) for f in fmaps_nhwc], level=lvl)
-        return Fn.RoiPool.apply(rois, n_roi, pe_f, pe_t, cfg.img_height, cfg.img_width, *fmaps_nhwc)
+        return Fn.RoiPool.apply(cfg.roi_pool_h, cfg.roi_pool_w, rois, n_roi, pe_f, pe_t, cfg.img_height, cfg.img_width, *fmaps_nhwc)
 
     def forward(self, rois, conv_out):
         B, R = rois.shape[:2]

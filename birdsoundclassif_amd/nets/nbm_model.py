@@ -37,9 +37,10 @@ class NbmModel(nn.Module):
         the listed F(2x2,3x3) tiles gained nothing there (round 2: 10.1 -> 8.5 ms at B = 64, eaten by the RoI phase); with the
         pattern pixels going through the cell transforms (csrc/cellwino.hip: 25 plane products per 4x4 cell instead of the 64 of
         its four tiles) it pays: detect step 81.4 -> 75.6 ms at B = 64.
-        A RoI pool other than 2 x 2 reads dense maps (the tile lists and the footprint re-zeroing know the 2 x 2 windows only)."""
+        A RoI pool other than ops.ONDEMAND_POOL_HW reads dense maps (the tile lists and the footprint re-zeroing are built on its
+        windows only)."""
         a = self.args
-        if (getattr(a, 'roi_pool_h', 2), getattr(a, 'roi_pool_w', 2)) != (2, 2):
+        if (getattr(a, 'roi_pool_h', 2), getattr(a, 'roi_pool_w', 2)) != ops.ONDEMAND_POOL_HW:
             return None
         if getattr(a, 'fpn_first', False) or getattr(a, 'sandwich_attn', False) or getattr(a, 'fpn', 'fpn') != 'fpn':
             return None

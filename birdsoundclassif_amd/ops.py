@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import GconvBwdDesc, GconvDesc, GemmDesc, RoiDesc, RoiHwDesc, check
+from ._lib import GconvBwdDesc, GconvDesc, GemmDesc, RoiHwDesc, check
 
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_LEAKY = 0, 1, 2, 3
 
@@ -965,10 +965,15 @@ def nms_batched(boxes, scores, n_in, thresh, post_n, segments=None, force_big=Fa
     return rois, rs, n_out
 
 
+# The pool size the demand-driven FPN maps and the persistent gradient maps serve: the tile lists (nbm_roi_tiles) and the
+# footprint re-zeroing (nbm_zero_roi_windows) are built on its windows.
+ONDEMAND_POOL_HW = (2, 2)
+
+
 def roi_pool_plan(ph, pw, fmap_hw):
-    """Which RoI-pooling kernels serve a `--roi_pool_h` x `--roi_pool_w` pool on maps of the sizes `fmap_hw` [(h, w), ...]
-    -> 'fixed2x2' (nbm_roi_pool / nbm_roi_pool_bwd, the reference's default) or 'general' (nbm_roi_pool_hw / _bwd, dense
-    maps only).  Host-only; refuses the two pool sizes the reference itself cannot run."""
+    """What a `--roi_pool_h` x `--roi_pool_w` pool on maps of the sizes `fmap_hw` [(h, w), ...] may read and write
+    -> 'ondemand' (ONDEMAND_POOL_HW: demand-driven maps, persistent gradient maps) or 'dense' (dense maps only); the kernels
+    are the same.  Host-only; refuses the two pool sizes the reference itself cannot run."""
     ph, pw = int(ph), int(pw)
     if ph < 2 or pw < 2:
         raise ValueError(f'--roi_pool_h {ph} / --roi_pool_w {pw}: a pool below 2 x 2 is no configuration of the reference -- its '
@@ -978,19 +983,18 @@ def roi_pool_plan(ph, pw, fmap_hw):
     if ph > mh or pw > mw:
         raise ValueError(f'--roi_pool_h {ph} / --roi_pool_w {pw} exceeds the smallest pyramid map ({mh} x {mw}): the '
                          "reference's growth loop (layers.py:459-465) does not terminate when a window cannot reach the pool size")
-    return 'fixed2x2' if (ph, pw) == (2, 2) else 'general'
+    return 'ondemand' if (ph, pw) == ONDEMAND_POOL_HW else 'dense'
 
 
-def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=(2, 2), force_general=False):
+def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=ONDEMAND_POOL_HW):
     """fmaps: list of NHWC [B,h,w,C]; rois [B,cap,4]; n_roi device int32 [B] (or [1], `roi_counts`) -> pool,
-    pe [B*cap,ph,pw,C], level [B,cap].  `pool_hw` other than (2, 2) runs nbm_roi_pool_hw (dense maps); `force_general` sends
-    2 x 2 there too (tests: its outputs are the bits of nbm_roi_pool)."""
+    pe [B*cap,ph,pw,C], level [B,cap].  Rows of slots past n_roi, and of RoIs whose window has no pixel in the map, stay zero."""
     B, cap = rois.shape[:2]
     ph, pw = int(pool_hw[0]), int(pool_hw[1])
-    general = roi_pool_plan(ph, pw, [tuple(f.shape[1:3]) for f in fmaps]) == 'general' or force_general
+    roi_pool_plan(ph, pw, [tuple(f.shape[1:3]) for f in fmaps])
     n_roi = roi_counts(n_roi, B)
     C_ = fmaps[0].shape[-1]
-    d = RoiHwDesc() if general else RoiDesc()
+    d = RoiHwDesc()
     for i, f in enumerate(fmaps):
         _chk(f, name=f'fmap{i}')
         d.fmap[i] = f.data_ptr()
@@ -1002,11 +1006,8 @@ def roi_pool(fmaps, rois, n_roi, pe_f, pe_t, img_h, img_w, pool_hw=(2, 2), force
     pe = torch.zeros((B * cap, ph, pw, C_), device=rois.device, dtype=torch.float32)
     level = torch.zeros((B, cap), device=rois.device, dtype=torch.int32)
     d.pool, d.pe, d.level = pool.data_ptr(), pe.data_ptr(), level.data_ptr()
-    if general:
-        d.pool_h, d.pool_w = ph, pw
-        check(lib().nbm_roi_pool_hw(C.byref(d), _stream()), 'nbm_roi_pool_hw')
-    else:
-        check(lib().nbm_roi_pool(C.byref(d), _stream()), 'nbm_roi_pool')
+    d.pool_h, d.pool_w = ph, pw
+    check(lib().nbm_roi_pool_hw(C.byref(d), _stream()), 'nbm_roi_pool_hw')
     return pool, pe, level
 
 
@@ -1542,16 +1543,16 @@ def bn_train_bwd(g2d, x2d, mean, invstd, w):
     return gx, gw, gb
 
 
-def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None, force_general=False):
+def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None):
     """gpool [B*R,ph,pw,C] -> list of zero-initialised-then-accumulated gradient maps (NHWC) for the FPN levels.
     `pooled` {level index: stride of the RPN's depthwise convolution on that map}: those maps come from the persistent pool of
     `ondemand.zero_acquire` (demand-driven levels: the consumer of the gradient recycles them) instead of a fresh fill.
-    The pool size is gpool's; other than 2 x 2 (or `force_general`) runs nbm_roi_pool_hw_bwd, on dense maps only: the
-    footprint re-zeroing of the persistent maps knows the 2 x 2 windows alone."""
+    The pool size is gpool's; a 'dense' one (roi_pool_plan) takes no persistent map: the footprint re-zeroing knows the
+    windows of ONDEMAND_POOL_HW alone."""
     B, R = rois.shape[:2]
     ph, pw, C_ = gpool.shape[1:]
-    general = roi_pool_plan(ph, pw, [s[1:3] for s in fmap_shapes]) == 'general' or force_general
-    if general and (pooled or any(e is not None for _, e in (bases or {}).values())):
+    dense = roi_pool_plan(ph, pw, [s[1:3] for s in fmap_shapes]) == 'dense'
+    if dense and (pooled or any(e is not None for _, e in (bases or {}).values())):
         raise NotImplementedError('roi_pool_bwd: persistent (demand-driven) gradient maps exist for the 2 x 2 pool only')
     gf = []
     for i, s in enumerate(fmap_shapes):
@@ -1584,12 +1585,8 @@ def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None, force
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in gf])
     fh = (C.c_int * n)(*[s[1] for s in fmap_shapes])
     fw = (C.c_int * n)(*[s[2] for s in fmap_shapes])
-    if general:
-        check(lib().nbm_roi_pool_hw_bwd(ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, ph, pw, _ptr(_chk(gpool)),
-                                        _stream()), 'nbm_roi_pool_hw_bwd')
-        return gf
-    check(lib().nbm_roi_pool_bwd(ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, _ptr(_chk(gpool)), _stream()),
-          'nbm_roi_pool_bwd')
+    check(lib().nbm_roi_pool_hw_bwd(ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, ph, pw, _ptr(_chk(gpool)),
+                                    _stream()), 'nbm_roi_pool_hw_bwd')
     return gf
 
 

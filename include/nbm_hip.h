@@ -236,7 +236,8 @@ int nbm_wino23_conv_fused(const float* R, const float* U, const float* scale, co
  *   nbm_wino23_rows_tiles:       row half of the input transform for the four columns of every listed tile;
  *   nbm_wino23_conv_fused_tiles: as nbm_wino23_conv_fused, writes ONLY the pixels of the listed tiles;
  *   nbm_roi_tiles:               builds such a list on the device from the RoI windows (exactly the windows nbm_roi_pool
- *                                reads; n_roi: device int32 [B], one count per image) of pyramid level `level`, without the tiles flagged in skip [TH * TW] (optional);
+ *                                reads, one shared device function; a window with no pixel in the map lists no tile;
+ *                                n_roi: device int32 [B], one count per image) of pyramid level `level`, without the tiles flagged in skip [TH * TW] (optional);
  *                                dilate > 0: the tiles within `dilate` pixels of a window instead (where the data gradient of
  *                                a 3x3 convolution of those windows is non-zero);
  *                                tiles must hold B * ceil(TH * TW / 128) * 128 entries; writes *n_blocks. */
@@ -554,32 +555,21 @@ int nbm_nms_big_workspace(int B, int cap, int64_t* bytes);
 int nbm_nms_big(const float* boxes, const float* scores, const int* n_in, int B, int cap, float thresh, int post_n,
                 void* ws, int64_t ws_bytes, float* rois, float* roi_scores, int* n_out, const int* seg, void* stream);
 
-/* ROIPooling (layers.py:406-497): level assignment, window, 2x2 adaptive average of the FPN map and of
- * the separable positional encoding.  fmaps: 5 device pointers (NHWC, C channels); pe_f [img_h][C/2],
- * pe_t [img_w][C/2].  n_roi[b] RoIs in image b out of roi_cap slots.  Outputs NHWC [B*roi_cap][2][2][C]. */
-typedef struct nbm_roi_desc {
-  const float* fmap[5];
-  int fh[5], fw[5];
-  int n_levels, C;
-  const float* rois;     /* [B][roi_cap][4] */
-  const int* n_roi;      /* device int32 [B] */
-  int B, roi_cap;
-  const float* pe_f; const float* pe_t; int img_h, img_w;
-  float* pool; float* pe; int* level;
-} nbm_roi_desc;
-int nbm_roi_pool(const nbm_roi_desc* d, void* stream);
-
-/* ROIPooling (layers.py:406-497) at any pool size (train.py:115-117, --roi_pool_h / --roi_pool_w): the fields of nbm_roi_desc
- * plus pool_h, pool_w.  Level assignment, rounding, the y2 clamp and the clamped x2 for the map / unclamped x2 for the encoding
- * are those of nbm_roi_pool; the window is grown to at least pool_h x pool_w (layers.py:459-465, as a loop bounded by the pool
- * size), bins are [floor(i*h/ph), ceil((i+1)*h/ph)) x [floor(j*w/pw), ceil((j+1)*w/pw)), each summed row-major in fp32 and
- * divided once by its area; the positional encoding is accumulated in double and rounded once.  pool_h = pool_w = 2 gives the
- * bits of nbm_roi_pool.  The maps are dense.  One workgroup per RoI slot, 16-byte accesses along C when C % 4 == 0 and the map
- * and output pointers are 16-byte aligned, 4-byte accesses otherwise.  Slots r >= n_roi[b] are left untouched.
+/* ROIPooling (layers.py:406-497) at any pool size (train.py:115-117, --roi_pool_h / --roi_pool_w).  fmaps: n_levels device
+ * pointers (NHWC, C channels); pe_f [img_h][C/2], pe_t [img_w][C/2].  n_roi[b] RoIs in image b out of roi_cap slots.
+ * Level assignment (layers.py:408-417), rounding, the y2 clamp, the clamped x2 for the map / unclamped x2 for the encoding;
+ * the window is grown to at least pool_h x pool_w (layers.py:459-465, as a loop bounded by the pool size), bins are
+ * [floor(i*h/ph), ceil((i+1)*h/ph)) x [floor(j*w/pw), ceil((j+1)*w/pw)), each summed row-major in fp32 and divided once by its
+ * area; the positional encoding is accumulated in double and rounded once.  One window function (csrc/roipool.hip) serves these
+ * kernels, nbm_roi_tiles and nbm_zero_roi_windows.  A RoI whose window has no pixel in the map (coordinates outside the image):
+ * its level is written, nothing else is read or written -- with zeroed outputs its rows stay zero.
+ * Only the window of a RoI is read, so a demand-driven map whose tiles under the RoIs are computed (nbm_roi_tiles) serves as well
+ * as a dense one.  One workgroup per RoI slot, 16-byte accesses along C when C % 4 == 0 and the map and output pointers are
+ * 16-byte aligned, 4-byte accesses otherwise.  Slots r >= n_roi[b] are left untouched.
  * Outputs NHWC [B*roi_cap][pool_h][pool_w][C].
  * Refused before any launch, nothing written: NBM_EUNSUPPORTED for pool_h < 2 or pool_w < 2 (the reference's one-row
  * positional-encoding slice layers.py:484 is empty, its mean NaN) and for pool_h > min(fh) or pool_w > min(fw) (the reference's
- * growth loop does not terminate); NBM_EINVAL for n_levels outside 1..5, odd C, null pointers. */
+ * growth loop does not terminate); NBM_EINVAL for n_levels outside 1..5, odd C, a map below 2 x 2, null pointers. */
 typedef struct nbm_roi_hw_desc {
   const float* fmap[5];
   int fh[5], fw[5];
@@ -592,6 +582,20 @@ typedef struct nbm_roi_hw_desc {
   int pool_h, pool_w;
 } nbm_roi_hw_desc;
 int nbm_roi_pool_hw(const nbm_roi_hw_desc* d, void* stream);
+
+/* The reference's default pool: nbm_roi_pool_hw with pool_h = pool_w = 2 (nbm_roi_desc is nbm_roi_hw_desc without the pool
+ * size), same kernel, same argument checks.  Outputs NHWC [B*roi_cap][2][2][C]. */
+typedef struct nbm_roi_desc {
+  const float* fmap[5];
+  int fh[5], fw[5];
+  int n_levels, C;
+  const float* rois;     /* [B][roi_cap][4] */
+  const int* n_roi;      /* device int32 [B] */
+  int B, roi_cap;
+  const float* pe_f; const float* pe_t; int img_h, img_w;
+  float* pool; float* pe; int* level;
+} nbm_roi_desc;
+int nbm_roi_pool(const nbm_roi_desc* d, void* stream);
 
 /* FastRCNN eval post-processing (layers.py:688-776) for B images, n_roi[b] RoIs in image b:
  * class arg-max, per-class delta gather, decode+clip, sort by score, drop background, class-agnostic
@@ -726,7 +730,7 @@ int nbm_weighted_sum_bwd(const float* x0, const float* x1, const float* x2, cons
                          float* gx1, float* gx2, float* gw, int64_t n, void* stream);
 /* Targeted re-zeroing of a gradient map [B][H][W][C] (C % 4 == 0) that is zero except for known footprints -- the gradient of
  * a demand-driven FPN map (training): what RoiPooling's backward scattered into the windows of level `lvl` (the windows of
- * nbm_roi_pool_bwd), what the stride-`stride` depthwise convolution's backward added on its 3x3 blocks (layers.py:62-65), and
+ * nbm_roi_pool_bwd, one shared device function; a window with no pixel in the map zeroes nothing), what the stride-`stride` depthwise convolution's backward added on its 3x3 blocks (layers.py:62-65), and
  * the 2x2 tiles of a list (layout of nbm_roi_tiles; n_blocks optional device count).  The map can then be kept across steps
  * instead of being filled (12.6 + 18.9 GB per step at B = 128) -- there is no reference counterpart, autograd allocates. */
 int nbm_zero_roi_windows(float* g, int H, int W, int C, const float* rois /*[B][n_roi][4]*/, const int* level /*[B][n_roi]*/,
@@ -787,9 +791,6 @@ int nbm_bn_train_fwd(const float* x, int64_t M, int C, const float* w, const flo
                      float* run_mean, float* run_var, double* stats_ws, float* mean, float* invstd, float* y, void* stream);
 int nbm_bn_train_bwd(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd,
                      const float* w, double* red_ws, float* gx, float* gw, float* gb, void* stream);
-/* ROIPooling backward: scatter-add of gpool [B*n_roi][2][2][C] into the (zeroed) FPN gradient maps */
-int nbm_roi_pool_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
-                     const float* rois, const int* level, int B, int n_roi, const float* gpool, void* stream);
 /* ROIPooling backward at any pool size (autograd of layers.py:406-497 with --roi_pool_h / --roi_pool_w): scatter-add of
  * gpool [B*n_roi][pool_h][pool_w][C] into the given gradient maps, windows and bins of nbm_roi_pool_hw on the levels in
  * `level`.  The sums are fp32 atomics: RoI windows overlap, so their order -- and the last bits of the result -- is not fixed.
@@ -797,6 +798,9 @@ int nbm_roi_pool_bwd(float* const* gfmap_host, const int* fh_host, const int* fw
 int nbm_roi_pool_hw_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
                         const float* rois, const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
                         void* stream);
+/* nbm_roi_pool_hw_bwd with pool_h = pool_w = 2 (gpool [B*n_roi][2][2][C]): same kernel, same argument checks */
+int nbm_roi_pool_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
+                     const float* rois, const int* level, int B, int n_roi, const float* gpool, void* stream);
 /* out[0] += sum g^2 (double); then AdamW on a flat range with the clip coefficient min(1, max_norm/(sqrt(*sqnorm)+1e-6))
  * evaluated on device (sqnorm NULL or max_norm <= 0: no clipping). */
 int nbm_sqnorm_accum(const float* g, int64_t n, double* out, void* stream);

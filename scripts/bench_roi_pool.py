@@ -1,4 +1,4 @@
-"""RoI pooling forward and backward: the fixed 2 x 2 kernels beside the general ones; prints a table and one JSON line.
+"""RoI pooling forward and backward at several pool sizes; prints a table and one JSON line.
 
     python scripts/bench_roi_pool.py [--rounds 7] [--window_ms 40] [--skip_steps] [--out profiles/roi_pool.txt]
 
@@ -6,8 +6,7 @@ Dense random FPN maps of the real sizes (C = 256) and seeded boxes spread over a
 image (the evaluation step) and at B = 128 with 1 000 (the negative training step).  The library entry points are called
 directly on preallocated outputs (no fills in the timed region), HIP events around windows of about --window_ms of
 back-to-back calls after a warm-up, --rounds windows per variant, the variants of one leg alternating; median, minimum and
-maximum per call.  Variants: nbm_roi_pool / nbm_roi_pool_bwd (2 x 2), nbm_roi_pool_hw / nbm_roi_pool_hw_bwd at 2 x 2, 3 x 3 and
-7 x 7.  `bytes` is what a launch has to move -- the window pixels once (twice for the backward pass: an atomic reads and
+maximum per call.  Variants: nbm_roi_pool_hw / nbm_roi_pool_hw_bwd at 2 x 2, 3 x 3 and 7 x 7.  `bytes` is what a launch has to move -- the window pixels once (twice for the backward pass: an atomic reads and
 writes) plus the pooled rows -- and `of peak` that figure over the median time as a fraction of 6.3 TB/s.
 
 Without --skip_steps: the eager detect step at B = 64 and one positive training step at B = 128 with `--roi_pool_h 3
@@ -97,9 +96,8 @@ def pool_leg(B, R, rounds, window_ms):
     fh = (ctypes.c_int * n)(*[h for h, _ in FMAP_HW])
     fw = (ctypes.c_int * n)(*[w for _, w in FMAP_HW])
     variants, info, keep = {}, {}, []
-    for name, ph, pw, general in (('2x2 fixed', 2, 2, False), ('2x2 general', 2, 2, True), ('3x3 general', 3, 3, True),
-                                  ('7x7 general', 7, 7, True)):
-        d = _lib.RoiHwDesc() if general else _lib.RoiDesc()
+    for name, ph, pw in (('2x2', 2, 2), ('3x3', 3, 3), ('7x7', 7, 7)):
+        d = _lib.RoiHwDesc()
         for i, f in enumerate(fm):
             d.fmap[i], d.fh[i], d.fw[i] = f.data_ptr(), f.shape[1], f.shape[2]
         pool = torch.zeros(B * R, ph, pw, C_FPN, device='cuda')
@@ -110,30 +108,20 @@ def pool_leg(B, R, rounds, window_ms):
         d.n_levels, d.C, d.rois, d.n_roi, d.B, d.roi_cap = n, C_FPN, rois.data_ptr(), n_roi.data_ptr(), B, R
         d.pe_f, d.pe_t, d.img_h, d.img_w = pe_f.data_ptr(), pe_t.data_ptr(), IMG_H, IMG_W
         d.pool, d.pe, d.level = pool.data_ptr(), pe.data_ptr(), level.data_ptr()
-        if general:
-            d.pool_h, d.pool_w = ph, pw
+        d.pool_h, d.pool_w = ph, pw
 
-            def fwd(d=d):
-                ops.check(lib.nbm_roi_pool_hw(ctypes.byref(d), st), 'nbm_roi_pool_hw')
+        def fwd(d=d):
+            ops.check(lib.nbm_roi_pool_hw(ctypes.byref(d), st), 'nbm_roi_pool_hw')
 
-            def bwd(level=level, gpool=gpool, ph=ph, pw=pw):
-                ops.check(lib.nbm_roi_pool_hw_bwd(ptrs, fh, fw, n, C_FPN, rois.data_ptr(), level.data_ptr(), B, R, ph, pw,
-                                                  gpool.data_ptr(), st), 'nbm_roi_pool_hw_bwd')
-        else:
-            def fwd(d=d):
-                ops.check(lib.nbm_roi_pool(ctypes.byref(d), st), 'nbm_roi_pool')
-
-            def bwd(level=level, gpool=gpool):
-                ops.check(lib.nbm_roi_pool_bwd(ptrs, fh, fw, n, C_FPN, rois.data_ptr(), level.data_ptr(), B, R, gpool.data_ptr(), st),
-                          'nbm_roi_pool_bwd')
+        def bwd(level=level, gpool=gpool, ph=ph, pw=pw):
+            ops.check(lib.nbm_roi_pool_hw_bwd(ptrs, fh, fw, n, C_FPN, rois.data_ptr(), level.data_ptr(), B, R, ph, pw,
+                                              gpool.data_ptr(), st), 'nbm_roi_pool_hw_bwd')
         fwd()                                          # `level` for the backward pass
         px = window_pixels(rois_h, ph, pw)
         rows = B * R * ph * pw
         variants['fwd ' + name], variants['bwd ' + name] = fwd, bwd
         info['fwd ' + name] = {'bytes': 4 * C_FPN * (px + 2 * rows)}
         info['bwd ' + name] = {'bytes': 4 * C_FPN * (2 * px + rows)}
-    a, b = keep[0], keep[5]
-    assert torch.equal(a.view(torch.int32), b.view(torch.int32)), 'the general kernel at 2x2 differs from the fixed one'
     res = alternate(variants, rounds, window_ms)
     for name, s in res.items():
         s.update(info[name])

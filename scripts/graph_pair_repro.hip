@@ -1,6 +1,6 @@
 // Torch-free, library-free control experiment for DESIGN 4d: captured graph execs alive together in one process, each a chain of
 // kernel nodes (large by-value argument structs, a data dependency from node to node through device memory) with MEMSET nodes in
-// between, like the product's detect step (csrc/detect.hip: the counters of rpn_select / roi_tiles are zeroed by hipMemsetAsync).
+// between, like the product's detect step (csrc/detect.hip, csrc/roipool.hip: the counters of rpn_select / roi_tiles are zeroed by hipMemsetAsync).
 // Every kernel checks the checksum of its own argument struct and logs which (graph, node) block it saw; every memset node is
 // followed by a kernel that checks that the memset HAS happened and dirties the region again.  No kernel takes a pointer argument:
 // a corrupted argument cannot turn into a wild access.

@@ -13,7 +13,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from birdsoundclassif_amd import ops, synth          # noqa: E402
+from birdsoundclassif_amd import _lib, ops, synth    # noqa: E402
 import detect_ref as D                               # noqa: E402
 from helpers import filler_state_dict                # noqa: E402
 from oracle import nets_ref as O                     # noqa: E402
@@ -373,13 +373,78 @@ def test_roi_pool_backward_on_the_edge_rois():
     pool.backward(gp)
     fmd = [f.detach().permute(0, 2, 3, 1).contiguous().cuda().requires_grad_(True) for f in fm]
     pe_f, pe_t = _pe_tables()
-    pd, _, _ = Fn.RoiPool.apply(rois.cuda(), i32([R] * B), pe_f, pe_t, IMG_H, IMG_W, *fmd)
+    pd, _, _ = Fn.RoiPool.apply(2, 2, rois.cuda(), i32([R] * B), pe_f, pe_t, IMG_H, IMG_W, *fmd)
     pd.backward(gp.permute(0, 1, 3, 4, 2).reshape(B * R, 2, 2, C_ROI).contiguous().cuda())
     for i in range(len(fm)):
         assert fm[i].grad is not None
         got, ref = fmd[i].grad.cpu().permute(0, 3, 1, 2), fm[i].grad
         err, scale = float((got - ref).abs().max()), float(ref.abs().max())
         assert err <= 1e-5 * scale, f'level {i}: max err {err:.3e} vs scale {scale:.3e}'
+
+
+def test_the_2x2_abi_entries_forward_to_the_general_ones():
+    """nbm_roi_pool through a nbm_roi_desc gives the bits of ops.roi_pool(..., pool_hw=(2, 2)) (nbm_roi_pool_hw); nbm_roi_pool_bwd
+    equals nbm_roi_pool_hw_bwd(..., 2, 2, ...) within 1e-5 of the largest gradient (the atomic scatter's order is not fixed)."""
+    rois = _all_rois().cuda()
+    B, R = rois.shape[:2]
+    fm = [D.rnd(('edge_fm', i), B, C_ROI, h, w).permute(0, 2, 3, 1).contiguous().cuda() for i, (h, w) in enumerate(D.FMAP_HW)]
+    pe_f, pe_t = _pe_tables()
+    n_roi = i32([R, 0, 77])
+    ref = ops.roi_pool(fm, rois, n_roi, pe_f, pe_t, IMG_H, IMG_W, pool_hw=(2, 2))
+    outs = [torch.zeros_like(t) for t in ref]
+    d = _lib.RoiDesc()
+    for i, f in enumerate(fm):
+        d.fmap[i], d.fh[i], d.fw[i] = f.data_ptr(), f.shape[1], f.shape[2]
+    d.n_levels, d.C, d.rois, d.n_roi, d.B, d.roi_cap = len(fm), C_ROI, rois.data_ptr(), n_roi.data_ptr(), B, R
+    d.pe_f, d.pe_t, d.img_h, d.img_w = pe_f.data_ptr(), pe_t.data_ptr(), IMG_H, IMG_W
+    d.pool, d.pe, d.level = (t.data_ptr() for t in outs)
+    assert ops.lib().nbm_roi_pool(ctypes.byref(d), ops._stream()) == 0
+    for got, want, what in zip(outs, ref, ('pool', 'pe', 'level')):
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), what
+    assert bool(ref[0].any()) and bool(ref[2].any())
+
+    level = ops.roi_pool(fm, rois, i32([R] * B), pe_f, pe_t, IMG_H, IMG_W)[2]
+    gpool = D.rnd('edge_gp', B * R, 2, 2, C_ROI).cuda()
+    n = len(fm)
+    fh = (ctypes.c_int * n)(*[h for h, _ in D.FMAP_HW])
+    fw = (ctypes.c_int * n)(*[w for _, w in D.FMAP_HW])
+    maps = []
+    for hw in (False, True):
+        gf = [torch.zeros_like(f) for f in fm]
+        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in gf])
+        head = (ptrs, fh, fw, n, C_ROI, rois.data_ptr(), level.data_ptr(), B, R)
+        if hw:
+            rc = ops.lib().nbm_roi_pool_hw_bwd(*head, 2, 2, gpool.data_ptr(), ops._stream())
+        else:
+            rc = ops.lib().nbm_roi_pool_bwd(*head, gpool.data_ptr(), ops._stream())
+        assert rc == 0
+        maps.append(gf)
+    for i, (got, want) in enumerate(zip(*maps)):
+        err, scale = float((got - want).abs().max()), float(want.abs().max())
+        assert scale > 0 and err <= 1e-5 * scale, f'level {i}: max err {err:.3e} vs scale {scale:.3e}'
+
+
+def test_zero_roi_windows_zeroes_exactly_the_oracle_windows():
+    """nbm_zero_roi_windows on maps filled with -777, levels 0 and 1: the pixels under the oracle's 2 x 2 windows of that level
+    (O.roi_geometry, the windows of D.tiles_ref) are zero, every other value is still -777; slots on another level touch nothing."""
+    rois = _all_rois()
+    B, R = rois.shape[:2]
+    lvl, x1, y1, x2, y2 = O.roi_geometry(O.make_cfg(), rois, [h for h, _ in D.FMAP_HW], [w for _, w in D.FMAP_HW])
+    rois_d, lvl_d = rois.cuda(), lvl.int().cuda()
+    for level in (0, 1):
+        H, W = D.FMAP_HW[level]
+        want = torch.full((B, H, W), -777.0)
+        for b in range(B):
+            for r in range(R):
+                if int(lvl[b, r]) == level:
+                    want[b, int(y1[b, r]):int(y2[b, r]) + 1, int(x1[b, r]):min(int(x2[b, r]), W - 1) + 1] = 0.0
+        assert 100 < int((want == 0).sum()) < want.numel() // 2
+        for levels, expect in ((lvl_d, want), (torch.full_like(lvl_d, 2), torch.full_like(want, -777.0))):
+            g = torch.full((B, H, W, C_ROI), -777.0, device='cuda')
+            rc = ops.lib().nbm_zero_roi_windows(ops._ptr(g), H, W, C_ROI, ops._ptr(rois_d), ops._ptr(levels), B, R, level,
+                                                ops._stream())
+            assert rc == 0
+            assert torch.equal(g.cpu(), expect[..., None].expand(-1, -1, -1, C_ROI)), level
 
 
 # =============================================================================================== nbm_rcnn_post

@@ -1,5 +1,5 @@
 """GPU tests of the demand-driven finest FPN map (ondemand.conv3x3_winograd_lazy / lazy_complete, csrc/wino_fused.hip *_tiles,
-csrc/detect.hip roi_tiles): the listed tiles are bit-identical to the dense convolution, the tile lists are exactly the
+csrc/roipool.hip roi_tiles): the listed tiles are bit-identical to the dense convolution, the tile lists are exactly the
 tiles the consumers read, nothing reads an unwritten pixel (NaN poison), and detections / losses / gradients do not change."""
 import numpy as np
 import pytest

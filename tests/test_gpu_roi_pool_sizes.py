@@ -1,4 +1,4 @@
-"""GPU: the general RoI-pooling kernels (csrc/roipool.hip: nbm_roi_pool_hw / nbm_roi_pool_hw_bwd) at pool sizes other than
+"""GPU: the RoI-pooling kernels (csrc/roipool.hip: nbm_roi_pool_hw / nbm_roi_pool_hw_bwd) at pool sizes other than
 2 x 2, on the level-boundary and edge RoIs of tests/detect_ref.py and the real map sizes, against the CPU oracle
 (`oracle.nets_ref.roi_pooling` with `roi_pool_h` / `roi_pool_w` set).
 
@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 from birdsoundclassif_amd import _lib, ops                           # noqa: E402
 from birdsoundclassif_amd.nets import functional as Fn               # noqa: E402
 import detect_ref as D                                               # noqa: E402
+from helpers import load_golden                                      # noqa: E402
 from oracle import nets_ref as O                                     # noqa: E402
 
 IMG_W, IMG_H = D.IMG_W, D.IMG_H
@@ -57,11 +58,11 @@ def nhwc(fmaps):
     return [f.permute(0, 2, 3, 1).contiguous().cuda() for f in fmaps]
 
 
-def device_pool(ph, pw, fmaps_d, n_roi, C=C_ROI, **kw):
+def device_pool(ph, pw, fmaps_d, n_roi, C=C_ROI):
     rois = all_rois()
     R = rois.shape[1]
     pe_f, pe_t = _pe_tables(C)
-    pool, pe, lvl = ops.roi_pool(fmaps_d, rois.cuda(), i32(n_roi), pe_f, pe_t, IMG_H, IMG_W, pool_hw=(ph, pw), **kw)
+    pool, pe, lvl = ops.roi_pool(fmaps_d, rois.cuda(), i32(n_roi), pe_f, pe_t, IMG_H, IMG_W, pool_hw=(ph, pw))
     assert pool.shape == (B * R, ph, pw, C) and pe.shape == pool.shape
     return (pool.view(B, R, ph, pw, C).permute(0, 1, 4, 2, 3).cpu(), pe.view(B, R, ph, pw, C).permute(0, 1, 4, 2, 3).cpu(),
             lvl.cpu())
@@ -152,14 +153,24 @@ def test_scalar_path_with_maps_that_are_not_16_byte_aligned():
     assert_pe_close(pe, ref_pe)
 
 
-def test_general_kernel_at_2x2_gives_the_bits_of_the_fixed_one():
-    R = all_rois().shape[1]
-    for fmaps in (D.modular_fmaps(B, C_ROI), [D.rnd(('hw22', i), B, C_ROI, h, w) for i, (h, w) in enumerate(D.FMAP_HW)]):
-        fm = nhwc(fmaps)
-        old = device_pool(2, 2, fm, [R, 0, 77])
-        new = device_pool(2, 2, fm, [R, 0, 77], force_general=True)
-        for a, b, what in zip(old, new, ('pool', 'pe', 'level')):
-            assert torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)), what
+def test_2x2_gives_the_bits_of_the_retired_fixed_kernel():
+    """tests/golden/roi_pool_2x2_fixed.npz holds what the retired 2 x 2-only kernel wrote on an MI355X (nbm_roi_pool of the
+    library built from the commit before its removal, loaded beside the new one: profiles/roi_pool_unify.md) for
+    D.modular_fmaps(3, 16), all_rois() and the counts [R, 0, 77]: `pool`, `pe` [348, 2, 2, 16] and `level` [348], the rows of
+    the valid slots in slot order.  The one kernel that is left gives those bits."""
+    g = load_golden('roi_pool_2x2_fixed.npz')
+    rois = all_rois()
+    R = rois.shape[1]
+    n_roi = [R, 0, 77]
+    pe_f, pe_t = _pe_tables()
+    pool, pe, lvl = ops.roi_pool(nhwc(D.modular_fmaps(B, C_ROI)), rois.cuda(), i32(n_roi), pe_f, pe_t, IMG_H, IMG_W, pool_hw=(2, 2))
+    valid = torch.cat([torch.arange(b * R, b * R + n) for b, n in enumerate(n_roi)])
+    assert len(valid) == 348
+    for got, what in ((pool, 'pool'), (pe, 'pe'), (lvl.view(-1), 'level')):
+        want = torch.from_numpy(g[what])
+        got = got.cpu()[valid].contiguous()
+        assert got.shape == want.shape, what
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), what
 
 
 def _backward_pair(ph, pw, bases=False):
@@ -173,7 +184,7 @@ def _backward_pair(ph, pw, bases=False):
     pool.backward(gp)
     fmd = [f.detach().permute(0, 2, 3, 1).contiguous().cuda().requires_grad_(True) for f in fm]
     pe_f, pe_t = _pe_tables()
-    pd, _, _ = Fn.RoiPoolHW.apply(ph, pw, rois.cuda(), i32([R] * B), pe_f, pe_t, IMG_H, IMG_W, *fmd)
+    pd, _, _ = Fn.RoiPool.apply(ph, pw, rois.cuda(), i32([R] * B), pe_f, pe_t, IMG_H, IMG_W, *fmd)
     share = []
     if bases:
         share = [D.rnd(('edge_base', i), *f.shape) for i, f in enumerate(fmd)]

@@ -18,10 +18,10 @@ C_ROI = 16
 
 
 def test_plan_picks_the_kernels_and_refuses_what_the_reference_cannot_run():
-    assert ops.roi_pool_plan(2, 2, D.FMAP_HW) == 'fixed2x2'
+    assert ops.roi_pool_plan(2, 2, D.FMAP_HW) == 'ondemand'
     for ph, pw in SIZES + [(5, 2), (2, 3), (3, 2)]:
-        assert ops.roi_pool_plan(ph, pw, D.FMAP_HW) == 'general', (ph, pw)
-    assert ops.roi_pool_plan(24, 64, [(188, 512), (24, 64)]) == 'general'        # `--dilation`: the coarsest map is 24 x 64
+        assert ops.roi_pool_plan(ph, pw, D.FMAP_HW) == 'dense', (ph, pw)
+    assert ops.roi_pool_plan(24, 64, [(188, 512), (24, 64)]) == 'dense'          # `--dilation`: the coarsest map is 24 x 64
     for ph, pw in [(1, 2), (2, 1), (0, 2), (1, 1), (-3, 4)]:
         with pytest.raises(ValueError, match=r'--roi_pool_h.*--roi_pool_w.*positional-encoding slice.*empty'):
             ops.roi_pool_plan(ph, pw, D.FMAP_HW)
