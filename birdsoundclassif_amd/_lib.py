@@ -121,6 +121,10 @@ SIGNATURES = {
     'nbm_upsample_bilinear_add': [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P],
     'nbm_softmax_rows': [_P, _L, _I, _L, _P],
     'nbm_dwconv3x3': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P, _I, _I, _P],
+    'nbm_dwconv_bn_act': [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _I, _P, _P],
+    'nbm_dwconv_pool_slots': [_I, _I, _I],
+    'nbm_dwconv_strip_rows': [],
+    'nbm_se_gate': [_P, _I, _I, _I, _F, _P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P],
     'nbm_silu': [_P, _P, _L, _P],
     'nbm_layernorm': [_P, _L, _I, _P, _P, _F, _P, _P],
     'nbm_mha_small': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _L, _L, _P, _F, _P],

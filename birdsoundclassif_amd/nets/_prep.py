@@ -87,6 +87,11 @@ def gconv(weight, groups):
     return _cached(weight, ('gconv', int(groups)), lambda: _gconv_fragments(weight.detach(), groups))
 
 
+def dw_taps(weight):
+    """Depthwise weights [C, 1, k, k] (checkpoint layout) -> tap-major [k * k, C] for `nbm_dwconv_bn_act` (16-byte loads along C)."""
+    return _cached(weight, 'dwtaps', lambda: weight.detach().reshape(weight.shape[0], -1).t().contiguous())
+
+
 def gconv_dgrad(weight, groups, scale=None):
     """The weights of the DATA-GRADIENT convolution of a grouped 3x3 layer (`nbm_gconv3x3_dgrad`), in the fragment order of `gconv`:
     transposed inside each group, rotated by 180 degrees, and with the FrozenBN `scale` [C] that multiplies the incoming gradient per
@@ -373,6 +378,21 @@ def value_of_lateral(lat_w, proj_w, val_w, val_b):
         return (wlo @ val_w.detach().double()).float().contiguous(), (wlo @ val_b.detach().double()).float().contiguous()
     others = [proj_w, val_w, val_b]
     return _cached(lat_w, 'vallat', make, extra=tuple(v for t in others for v in (t.data_ptr(), t._version)))
+
+
+def pad_attention(ws, Cp, dp):
+    """(wq, bq, wk, bk, wv, bv, wo, bo) of a SelfAttention module (C -> d -> C) zero-padded to Cp / dp: [dp, Cp] x 3 with [dp] biases,
+    wo [Cp, dp], bo [Cp].  Differentiable (F.pad)."""
+    wq, bq, wk, bk, wv, bv, wo, bo = ws
+    C_, d = wq.shape[1], wq.shape[0]
+    inner = lambda w_, b_: (F.pad(w_, (0, Cp - C_, 0, dp - d)), F.pad(b_, (0, dp - d)))
+    return (*inner(wq, bq), *inner(wk, bk), *inner(wv, bv), F.pad(wo, (0, dp - d, 0, Cp - C_)), F.pad(bo, (0, Cp - C_)))
+
+
+def attention_padded(ws, Cp, dp):
+    """`pad_attention` once per weight version (evaluation mode)."""
+    extra = tuple(v for t in ws[1:] for v in (t.data_ptr(), t._version))
+    return _cached(ws[0], ('attnpad', Cp, dp), lambda: tuple(t.detach().contiguous() for t in pad_attention(ws, Cp, dp)), extra=extra)
 
 
 def cat_rows(tag, *tensors):

@@ -7,7 +7,11 @@ stated here as parameter containers, and the forward is a chain of fp32-MFMA imp
 FrozenBatchNorm affine + ReLU + residual fused into the epilogues.  Activations are NHWC.
 The ResNeXt names (resnext50_32x4d, resnext101_32x8d, resnext101_64x4d) are the same body with grouped bottlenecks, whose 3x3 runs
 on `ops.gconv3x3` (csrc/gconv.hip) and trains through `Fn.GConv3x3` (csrc/gconv_bwd.hip) in training mode.
+The EfficientNet names (efficientnet_b0 .. efficientnet_b4; Tan & Le 2019, torchvision's module / state_dict names) are a body of MBConv
+blocks: 1x1 GEMMs, the depthwise kernel and the squeeze-and-excitation kernel of csrc/mbconv.hip, frozen and evaluation only.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -20,6 +24,24 @@ _RESNET_LAYERS = {'resnet50': [3, 4, 6, 3], 'resnet101': [3, 4, 23, 3], 'resnet1
 # ResNeXt (Xie et al. 2017; torchvision's names): name -> (layers, groups, base width); the taps keep the ResNet channel counts
 _RESNEXT = {'resnext50_32x4d': ([3, 4, 6, 3], 32, 4), 'resnext101_32x8d': ([3, 4, 23, 3], 32, 8),
             'resnext101_64x4d': ([3, 4, 23, 3], 64, 4)}
+# EfficientNet-B0 (Tan & Le 2019, table 1): (expand ratio, kernel, stride, in, out, repeats) per stage; name -> (width, depth) multiplier
+_EFFNET_BASE = ((1, 3, 1, 32, 16, 1), (6, 3, 2, 16, 24, 2), (6, 5, 2, 24, 40, 2), (6, 3, 2, 40, 80, 3), (6, 5, 1, 80, 112, 3),
+                (6, 5, 2, 112, 192, 4), (6, 3, 1, 192, 320, 1))
+_EFFICIENTNET = {'efficientnet_b0': (1.0, 1.0), 'efficientnet_b1': (1.0, 1.1), 'efficientnet_b2': (1.1, 1.2),
+                 'efficientnet_b3': (1.2, 1.4), 'efficientnet_b4': (1.4, 1.8)}
+_EFFNET_TAPS = (1, 2, 3, 5, 7)         # the reference's IntermediateLayerGetter return layers of `features`
+
+
+def _make_divisible(v, divisor=8):
+    """Nearest multiple of `divisor`, never below it, and one step up if rounding lost more than 10 %."""
+    new_v = max(divisor, int(v + divisor / 2) // divisor * divisor)
+    return new_v + divisor if new_v < 0.9 * v else new_v
+
+
+def efficientnet_stages(name):
+    """[(expand ratio, kernel, stride, in, out, repeats)] of the seven MBConv stages with the width / depth multipliers applied."""
+    width, depth = _EFFICIENTNET[name]
+    return [(t, k, s, _make_divisible(i * width), _make_divisible(o * width), int(math.ceil(n * depth))) for t, k, s, i, o, n in _EFFNET_BASE]
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -177,6 +199,81 @@ class _ResNetBody(nn.Module):
         return taps
 
 
+class _SqueezeExcitation(nn.Module):
+    """Parameter holder of torchvision's SqueezeExcitation: fc1 (C -> Csq) and fc2 (Csq -> C), 1x1 convolutions with bias."""
+
+    def __init__(self, channels, squeeze):
+        super().__init__()
+        self.fc1 = nn.Conv2d(channels, squeeze, 1)
+        self.fc2 = nn.Conv2d(squeeze, channels, 1)
+
+
+def _conv_norm(cin, cout, k, stride, groups, norm_layer):
+    return nn.Sequential(nn.Conv2d(cin, cout, k, stride=stride, padding=(k - 1) // 2, groups=groups, bias=False), norm_layer(cout))
+
+
+class _MBConv(nn.Module):
+    """One MBConv block, torchvision's names (`block.{i}`: [expand,] depthwise, SE, project).  Forward (no tape: the body is frozen):
+    expand 1x1 GEMM with norm + SiLU in the epilogue -> `ops.dwconv_bn_act` (norm + SiLU, and the pool partials) -> `ops.se_gate` (the gate,
+    folded into one copy of the project weights per image) -> the project 1x1 as a GEMM with groups = B, norm and the block input in its
+    epilogue.  The gated map is never written."""
+
+    def __init__(self, ratio, k, stride, cin, cout, norm_layer):
+        super().__init__()
+        cexp = _make_divisible(cin * ratio)
+        layers = [] if cexp == cin else [_conv_norm(cin, cexp, 1, 1, 1, norm_layer)]
+        layers += [_conv_norm(cexp, cexp, k, stride, cexp, norm_layer), _SqueezeExcitation(cexp, max(1, cin // 4)),
+                   _conv_norm(cexp, cout, 1, 1, 1, norm_layer)]
+        self.block = nn.Sequential(*layers)
+        self.k, self.stride, self.use_res = k, stride, stride == 1 and cin == cout
+
+    def forward(self, x):
+        *expand, dw, se, proj = self.block
+        o = x
+        for e in expand:
+            s, b = e[1].affine()
+            o = ops.conv2d(o, _prep.krsc(e[0].weight), scale=s, shift=b, act=ops.ACT_SILU)
+        s, b = dw[1].affine()
+        o, part = ops.dwconv_bn_act(o, _prep.dw_taps(dw[0].weight), self.k, self.stride, scale=s, shift=b, act=ops.ACT_SILU, pool=True)
+        _, wb = ops.se_gate(part, o.shape[1] * o.shape[2], se.fc1.weight.detach(), se.fc1.bias.detach(), se.fc2.weight.detach(),
+                            se.fc2.bias.detach(), wproj=_prep.krsc(proj[0].weight))
+        s, b = proj[1].affine()
+        return ops.conv1x1_per_image(o, wb, proj[0].weight.shape[0], scale=s, shift=b, residual=x if self.use_res else None)
+
+
+class _EfficientNetBody(nn.Sequential):
+    """torchvision's `efficientnet_bN().features` up to stage 7 under the reference's IntermediateLayerGetter (children '0' .. '7': the
+    stem and the seven MBConv stages; the 1x1 head convolution, index 8, and the classifier are not part of the detector); returns the
+    outputs of stages 1, 2, 3, 5, 7."""
+
+    def __init__(self, name, norm_layer):
+        stages = efficientnet_stages(name)
+        mods = [_conv_norm(3, stages[0][3], 3, 2, 1, norm_layer)]
+        for t, k, s, cin, cout, n in stages:
+            mods.append(nn.Sequential(*[_MBConv(t, k, s if i == 0 else 1, cin if i == 0 else cout, cout, norm_layer) for i in range(n)]))
+        super().__init__(*mods)
+        self.num_channels = [stages[i - 1][4] for i in _EFFNET_TAPS]
+
+    def stem(self, x, init_conv=None):
+        """x: NHWC image -> the stage-0 output.  The stem's zero padding surrounds the OUTPUT of init_conv (1 -> 3 channels, with a bias):
+        the bias is inside the image and not in the padding, so the two are not composed into one convolution -- `ops.init_conv` writes
+        the 3-channel image (three times the input, the smallest map of the network) and the stem reads it with its own padding."""
+        if init_conv is not None:
+            x = ops.init_conv(x, init_conv.weight.detach(), init_conv.bias.detach())
+        s, b = self[0][1].affine()
+        return ops.conv2d(x, _prep.krsc(self[0][0].weight), 3, 3, 2, 1, scale=s, shift=b, act=ops.ACT_SILU)
+
+    def forward(self, x, init_conv=None):
+        x = self.stem(x, init_conv)
+        taps = []
+        for i in range(1, 8):
+            for blk in self[i]:
+                x = blk(x)
+            if i in _EFFNET_TAPS:
+                taps.append(x)
+        return taps
+
+
 class BackboneBase(nn.Module):
 
     def __init__(self, backbone, name, in_channels, train_backbone):
@@ -185,7 +282,7 @@ class BackboneBase(nn.Module):
             if not train_backbone:
                 parameter.requires_grad_(False)
         self.body = backbone
-        self.num_channels = list(bcbk_channels['resnet'].values())
+        self.num_channels = list(getattr(backbone, 'num_channels', bcbk_channels['resnet'].values()))
         if in_channels != 3:
             self.init_conv = nn.Conv2d(in_channels, 3, 1)
         self.in_channels = in_channels
@@ -201,13 +298,25 @@ class BackboneBase(nn.Module):
 
 
 class Backbone(BackboneBase):
-    """ResNet backbone with frozen BatchNorm (reference backbone.py:116-132)."""
+    """ResNet / ResNeXt / EfficientNet backbone with frozen BatchNorm (reference backbone.py:116-132)."""
 
     def __init__(self, name, in_channels, train_backbone, dilation, norm_layer_name):
-        if name not in _RESNET_LAYERS and name not in _RESNEXT:
-            raise ValueError(f'not supported {name}: the accelerated path implements {sorted(_RESNET_LAYERS) + sorted(_RESNEXT)}')
+        if name not in _RESNET_LAYERS and name not in _RESNEXT and name not in _EFFICIENTNET:
+            raise ValueError(f'not supported {name}: the accelerated path implements '
+                             f'{sorted(_RESNET_LAYERS) + sorted(_RESNEXT) + sorted(_EFFICIENTNET)} (efficientnet_v2_* and vgg16_bn are not)')
         if norm_layer_name != 'frozen_batchnorm':
             raise NotImplementedError('only --norm_layer_backbone frozen_batchnorm (reference default) is implemented')
+        if name in _EFFICIENTNET:
+            if train_backbone:
+                raise NotImplementedError(f'fine-tuning the {name} body is not implemented (the depthwise and squeeze-and-excitation kernels '
+                                          'have no backward pass yet): train behind the frozen body with --lr_backbone 0')
+            if in_channels != 1:
+                raise NotImplementedError(f'{name}: only --inpt_channels 1 (reference default) is implemented')
+            # `dilation` has no effect: the reference passes replace_stride_with_dilation to the resn* names only (backbone.py:129-131)
+            super().__init__(_EfficientNetBody(name, FrozenBatchNorm2d), name, in_channels, False)
+            # the frozen body runs without a tape, so no gradient reaches init_conv; its learning rate is --lr_backbone = 0 anyway
+            self.init_conv.requires_grad_(False)
+            return
         layers, groups, base_width = _RESNEXT[name] if name in _RESNEXT else (_RESNET_LAYERS[name], 1, 64)
         super().__init__(_ResNetBody(layers, FrozenBatchNorm2d, dilation=dilation, groups=groups, base_width=base_width), name,
                          in_channels, train_backbone)
@@ -226,9 +335,11 @@ class Joiner(nn.Sequential):
         return self[0](x), None
 
 
-def build_backbone(args):
+def build_backbone(args, inference=False):
+    """`inference` (run_detection.load_model): the model will only be evaluated -- an EfficientNet checkpoint whose training arguments
+    hold an lr_backbone > 0 loads with its body frozen instead of being refused."""
     position_embedding = build_position_encoding(args)
-    train_backbone = args.lr_backbone > 0
+    train_backbone = args.lr_backbone > 0 and not (inference and args.backbone in _EFFICIENTNET)
     backbone = Backbone(args.backbone, args.inpt_channels, train_backbone, args.dilation, args.norm_layer_backbone)
     model = Joiner(backbone, position_embedding)
     model.num_channels = backbone.num_channels

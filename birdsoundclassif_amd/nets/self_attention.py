@@ -11,6 +11,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import ops
 from . import _prep, functional as Fn
@@ -85,9 +86,22 @@ class SelfAttention(nn.Module):
                 wv, bv = _prep.value_of_lateral(defer_projection.weight, self.final_projection.weight, wv, bv)
             _, _, cx, _ = Fn.attention_context(x.view(B, L, Cc), self.query.weight, self.query.bias, self.key.weight, self.key.bias, wv, bv, inv)
             return Projected(inpt, cx.view(B, h, w, -1), self.final_projection.weight, self.final_projection.bias, lat)
-        out = Fn.Attention.apply(x.view(B, L, Cc), self.query.weight, self.query.bias, self.key.weight, self.key.bias,
-                                 self.value.weight, self.value.bias, self.final_projection.weight,
-                                 self.final_projection.bias, inv).view(B, h, w, Cc)        # = x + attention(x)
+        if d % 32 or Cc % 32:
+            # widths that are no multiple of the GEMM's K-step (EfficientNet taps: 112 / 56, 120 / 60, ...): the module runs on operands
+            # zero-padded to the next multiple of 32 -- zero weight rows / columns and zero biases add exact zeros, so every sum keeps its
+            # value; the padding and the slice are differentiable copies, the gradients reach the parameters through them
+            Cp, dp = (Cc + 31) // 32 * 32, (d + 31) // 32 * 32
+            ws = (self.query.weight, self.query.bias, self.key.weight, self.key.bias, self.value.weight, self.value.bias,
+                  self.final_projection.weight, self.final_projection.bias)
+            if torch.is_grad_enabled():
+                ws = _prep.pad_attention(ws, Cp, dp)
+            else:
+                ws = _prep.attention_padded(ws, Cp, dp)
+            out = Fn.Attention.apply(F.pad(x, (0, Cp - Cc)).view(B, L, Cp), *ws, inv).view(B, h, w, Cp)[..., :Cc].contiguous()
+        else:
+            out = Fn.Attention.apply(x.view(B, L, Cc), self.query.weight, self.query.bias, self.key.weight, self.key.bias,
+                                     self.value.weight, self.value.bias, self.final_projection.weight,
+                                     self.final_projection.bias, inv).view(B, h, w, Cc)        # = x + attention(x)
         if self.position_encoding:                     # the pyramid's residual is the ORIGINAL map, not map + encoding
             out = Fn.AddConst.apply(out, self._half_pe(h, w, Cc, inpt.device, -1.0))
         return out

@@ -701,6 +701,76 @@ def dwconv3x3(x, w, bias, mult, stride=1, film=None):
     return y
 
 
+def dwconv_pool_slots(C_, Ho, Wo):
+    """Slots per image of the pool partials `dwconv_bn_act(pool=True)` writes for an output map of Ho x Wo x C."""
+    n = lib().nbm_dwconv_pool_slots(int(C_), int(Ho), int(Wo))
+    if n <= 0:
+        check(n, 'nbm_dwconv_pool_slots')
+    return n
+
+
+def dwconv_bn_act(x, w_taps, k, stride=1, scale=None, shift=None, act=ACT_NONE, pool=False):
+    """Depthwise k x k / stride / pad (k - 1) / 2 convolution of x [B,H,W,C] (k in {3, 5}, stride in {1, 2}, C % 4 == 0; what the kernel
+    does not implement raises: there is no slow path), y = act(conv * scale + shift).  `w_taps` [k * k, C] = `_prep.dw_taps(weight)`.
+    -> y [B,Ho,Wo,C], or with `pool` (y, part [B, slots, C]): every slot holds one workgroup's sum of y per channel (`se_gate` adds the
+    slots in a fixed order; a fresh tensor per call, fully written by the kernel)."""
+    _chk(x, name='x'), _chk(w_taps, name='w_taps')
+    if x.dim() != 4 or tuple(w_taps.shape) != (k * k, x.shape[3]):
+        raise ValueError(f'dwconv_bn_act: x must be [B,H,W,C] and w_taps [{k * k}, C], got {tuple(x.shape)} and {tuple(w_taps.shape)}')
+    B, H, W, C_ = x.shape
+    p = (k - 1) // 2
+    Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
+    for v, nm in ((scale, 'scale'), (shift, 'shift')):
+        if v is not None and _chk(v, name=nm).numel() != C_:
+            raise ValueError(f'dwconv_bn_act: {nm} must hold {C_} values')
+    y = torch.empty((B, Ho, Wo, C_), device=x.device, dtype=torch.float32)
+    part = torch.empty((B, dwconv_pool_slots(C_, Ho, Wo), C_), device=x.device, dtype=torch.float32) if pool and C_ % 4 == 0 else None
+    check(lib().nbm_dwconv_bn_act(_ptr(x), B, H, W, C_, int(k), int(stride), _ptr(w_taps), _ptr(scale), _ptr(shift), int(act), _ptr(y),
+                                  Ho, Wo, _ptr(part), _stream()), 'nbm_dwconv_bn_act')
+    return (y, part) if pool else y
+
+
+def se_gate(part, hw, w1, b1, w2, b2, wproj=None, w_ld=None, out=None):
+    """Squeeze-and-excitation gate from the pool partials of `dwconv_bn_act`: part [B, slots, C], hw = Ho * Wo of the pooled map, w1
+    [Csq, C], b1 [Csq], w2 [C, Csq], b2 [C] -> gate [B, C] = sigmoid(w2 silu(w1 mean + b1) + b2).  With `wproj` [N, >= C] (KRSC rows of the
+    project 1x1): (gate, wb [B, N, w_ld]) with wb[b, n, c] = wproj[n, c] * gate[b, c], w_ld = C rounded up to 32 (pad columns zero); `out`:
+    write wb there instead of into a fresh tensor."""
+    for t, nm in ((part, 'part'), (w1, 'w1'), (b1, 'b1'), (w2, 'w2'), (b2, 'b2')):
+        _chk(t, name=nm)
+    B, n_slots, C_ = part.shape
+    Csq = b1.numel()
+    if w1.numel() != Csq * C_ or w2.numel() != Csq * C_ or b2.numel() != C_:
+        raise ValueError(f'se_gate: weights do not fit {C_} channels squeezed to {Csq}')
+    gate = torch.empty((B, C_), device=part.device, dtype=torch.float32)
+    wb, N, wp_ld = None, 0, 0
+    if wproj is not None:
+        _chk(wproj, name='wproj')
+        N, wp_ld = wproj.shape
+        w_ld = (C_ + 31) // 32 * 32 if w_ld is None else int(w_ld)
+        wb = torch.empty((B, N, w_ld), device=part.device, dtype=torch.float32) if out is None else _chk(out, name='out')
+        if tuple(wb.shape) != (B, N, w_ld):
+            raise ValueError(f'se_gate: out must be [{B}, {N}, {w_ld}]')
+    check(lib().nbm_se_gate(_ptr(part), B, n_slots, C_, 1.0 / float(hw), _ptr(w1), _ptr(b1), Csq, _ptr(w2), _ptr(b2), _ptr(gate),
+                            _ptr(wproj), wp_ld, N, _ptr(wb), int(w_ld or 0), _stream()), 'nbm_se_gate')
+    return (gate, wb) if wproj is not None else gate
+
+
+def conv1x1_per_image(x, wb, N, scale=None, shift=None, residual=None, act=ACT_NONE):
+    """1x1 convolution with ONE WEIGHT MATRIX PER IMAGE: x [B,H,W,C], wb [B, N, w_ld] (`se_gate`) -> [B,H,W,N] =
+    act(x_b wb_b^T * scale + shift + residual): nbm_gemm_conv with groups = B (scale / shift are not strided by group)."""
+    _chk(x, name='x'), _chk(wb, name='wb')
+    B, H, W, C_ = x.shape
+    if wb.dim() != 3 or wb.shape[0] != B or wb.shape[1] != N or wb.shape[2] < C_:
+        raise ValueError(f'conv1x1_per_image: wb must be [{B}, {N}, >= {C_}], got {tuple(wb.shape)}')
+    y = torch.empty((B, H, W, N), device=x.device, dtype=torch.float32)
+    if residual is not None:
+        _chk(residual, name='residual')
+        assert residual.shape == y.shape
+    gemm_conv(x, wb, y, B=1, H=H, W=W, Cin=C_, N=N, w_ld=wb.shape[2], scale=scale, shift=shift, residual=residual, act=act,
+              groups=B, x_gs=H * W * C_, w_gs=N * wb.shape[2], y_gs=H * W * N, res_gs=H * W * N if residual is not None else 0)
+    return y
+
+
 def silu(x):
     _chk(x, name='x')
     y = torch.empty_like(x)

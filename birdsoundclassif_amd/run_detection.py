@@ -157,7 +157,7 @@ def load_model(mod_p):
         args = Args(**json.load(f))
     args.device = device          # placement follows this process, not the string stored in the file (Appendix C-13)
     setattr_others(args)
-    backbone = build_backbone(args)
+    backbone = build_backbone(args, inference=True)
     attn = build_sa_layers(args, backbone.num_channels)
     fpn = build_fpn(args, backbone.num_channels)
     head = build_head(args)

@@ -216,6 +216,31 @@ def label_rows(seed=0, n=40, filename='recA', duration=42.0):
 
 
 # --------------------------------------------------------------------------- filler weights
+_EFFNET_KEY = __import__('re').compile(r'backbone\.0\.body\.\d+\.(\d+\.block\.\d+\.)?(\d+|fc[12])\.[a-z_]+$')
+
+
+def _effnet_leaf(name, shape, n, seed):
+    """Filler of one EfficientNet body leaf (torchvision's names: `body.0.{0,1}.*` the stem, `body.S.B.block.I.{0,1}.*` convolution /
+    norm, `body.S.B.block.I.fc{1,2}.*` squeeze-and-excitation).  The generic rules tell a norm by its name ('.bn', '.norm') and would
+    draw these norms' running_var around zero.  He-scaled convolutions on their own fan-in (k * k for a depthwise one); the project norm,
+    the last of a block and the end of its residual branch, is damped like a bottleneck's bn3; the excite bias puts the gates around
+    0.7 with a spread, so that a wrong gate mapping changes the output and the gated maps do not fade over 16 - 32 blocks."""
+    parts = name.split('.')
+    leaf, mod = parts[-1], parts[-2]
+    if mod in ('fc1', 'fc2'):
+        if leaf == 'bias':
+            return 0.02 * normal(name, n, seed) if mod == 'fc1' else 1.0 + 0.5 * normal(name, n, seed)
+        return np.sqrt(2.0 / shape[1]) * normal(name, n, seed)
+    if mod == '1':                                           # FrozenBatchNorm2d
+        last = 'block' in parts and (parts[-3] == '3' or (parts[-3] == '2'))      # block.3 / (no expand) block.2: the project norm
+        if leaf == 'weight':
+            return (0.8 if last else 1.0) * (1.0 + 0.1 * normal(name, n, seed))
+        if leaf in ('bias', 'running_mean'):
+            return 0.05 * normal(name, n, seed)
+        return 0.9 + 0.2 * uniform(name, n, seed)
+    return np.sqrt(2.0 / int(np.prod(shape[1:]))) * normal(name, n, seed)
+
+
 def fill_state_dict(shapes, seed=0):
     """Deterministic filler for a {name: shape} mapping (SURVEY Appendix B layout): conv/linear
     weights ~ N(0, gain/fan_in), BatchNorm weight ~ 1, running_var ~ 1, small biases/means; the last
@@ -228,9 +253,12 @@ def fill_state_dict(shapes, seed=0):
         if name.endswith('num_batches_tracked'):
             out[name] = torch.zeros((), dtype=torch.int64)
             continue
+        if _EFFNET_KEY.search(name):
+            out[name] = torch.from_numpy(np.asarray(_effnet_leaf(name, shape, n, seed), dtype=np.float32).reshape(shape))
+            continue
         leaf = name.rsplit('.', 1)[-1]
         parent = name.rsplit('.', 1)[0]
-        is_norm = ('.bn' in name or '.norm' in name or 'downsample.1' in name)
+        is_norm =('.bn' in name or '.norm' in name or 'downsample.1' in name)
         if is_norm:
             if leaf == 'weight':
                 scale = 0.35 if parent.endswith('bn3') else 1.0

@@ -461,6 +461,25 @@ int nbm_dwconv3x3(const float* x, int B, int H, int W, int Cin, int mult, int st
                   const float* w /*[Cin*mult][9]*/, const float* bias, const float* film, int64_t film_ld,
                   float* y, int Ho, int Wo, void* stream);
 
+/* ---- MBConv (EfficientNet-B0..B4 bodies; csrc/mbconv.hip) -------------------------------------------------------
+ * Depthwise k x k convolution (k in {3, 5}, stride in {1, 2}, pad (k - 1) / 2, channel multiplier 1) of an NHWC map, then
+ * y = act(conv * scale[c] + shift[c]) with act in {NBM_ACT_NONE, NBM_ACT_SILU}; scale / shift may be NULL (1 / 0).
+ * w_taps [k * k][C]: tap-major weights (tap = r * k + s).  C % 4 == 0; anything else: NBM_EUNSUPPORTED (no slow path).
+ * Every output element is the sum of its k * k products in (r, s) order (zero products outside the image), whatever the launch shape.
+ * pool_part (or NULL) [B][nbm_dwconv_pool_slots(C, Ho, Wo)][C]: every slot is WRITTEN with one workgroup's sum of its activated
+ * outputs -- no atomics, no zero fill needed; the slots of image b depend on image b alone. */
+int nbm_dwconv_bn_act(const float* x, int B, int H, int W, int C, int k, int stride, const float* w_taps, const float* scale,
+                      const float* shift, int act, float* y, int Ho, int Wo, float* pool_part, void* stream);
+/* slots per image of pool_part for an output map of Ho x Wo x C (< 0: an error code); output rows per strip of a workgroup */
+int nbm_dwconv_pool_slots(int C, int Ho, int Wo);
+int nbm_dwconv_strip_rows(void);
+/* Squeeze-and-excitation behind nbm_dwconv_bn_act, one launch: mean[b][c] = inv_hw * (pool_part[b][0][c] + pool_part[b][1][c] + ...),
+ * s = silu(w1 mean + b1) (w1 [Csq][C]), gate[b] = sigmoid(w2 s + b2) (w2 [C][Csq]) -> gate [B][C].  Csq is any positive number.
+ * wb (or NULL) [B][N][w_ld], w_ld % 32 == 0, w_ld >= C: the project convolution's weights wproj [N][wp_ld >= C] with the gate folded
+ * in, wb[b][n][c] = wproj[n][c] * gate[b][c], columns C .. w_ld - 1 written as zeros -- the B operand of nbm_gemm_conv with groups = B. */
+int nbm_se_gate(const float* pool_part, int B, int n_slots, int C, float inv_hw, const float* w1, const float* b1, int Csq,
+                const float* w2, const float* b2, float* gate, const float* wproj, int wp_ld, int N, float* wb, int w_ld, void* stream);
+
 /* y = x * sigmoid(x) -- nn.SiLU (layers.py:31,41). */
 int nbm_silu(const float* x, float* y, int64_t n, void* stream);
 
