@@ -205,6 +205,9 @@ SIGNATURES = {
     'nbm_film_bwd': [_P, _P, _P, _P, _P, _L, _I, _P],
     'nbm_bn_train_fwd': [_P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P],
     'nbm_bn_train_bwd': [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    'nbm_bn_act_plan': [_L, _I, C.POINTER(C.c_int), C.POINTER(C.c_int64)],
+    'nbm_bn_act_train_fwd': [_P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P],
+    'nbm_bn_act_train_bwd': [_P, _P, _P, _L, _I, _P, _P, _P, _I, _P, _L, _P, _P, _P, _P, _P],
     'nbm_roi_pool_bwd': [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _P, _P, _I, _I, _P, _P],
     'nbm_roi_pool_hw_bwd': [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     'nbm_sqnorm_accum': [_P, _L, _P, _P],

@@ -9,6 +9,8 @@ The ResNeXt names (resnext50_32x4d, resnext101_32x8d, resnext101_64x4d) are the 
 on `ops.gconv3x3` (csrc/gconv.hip) and trains through `Fn.GConv3x3` (csrc/gconv_bwd.hip) in training mode.
 The EfficientNet names (efficientnet_b0 .. efficientnet_b4; Tan & Le 2019, torchvision's module / state_dict names) are a body of MBConv
 blocks: 1x1 GEMMs, the depthwise kernel and the squeeze-and-excitation kernel of csrc/mbconv.hip, frozen and evaluation only.
+`--norm_layer_backbone batchnorm` (ResNet / ResNeXt names) puts the live `BatchNorm2d` in place of FrozenBatchNorm2d: the same launches in
+eval mode, a chain of convolutions and `Fn.BatchNormAct` nodes (csrc/bnorm.hip) in training mode.
 """
 import math
 
@@ -65,8 +67,47 @@ class FrozenBatchNorm2d(nn.Module):
         return _prep.bn_affine(self.weight, self.bias, self.running_mean, self.running_var, 1e-5, frozen=True)
 
 
+class BatchNorm2d(nn.BatchNorm2d):
+    """Live BatchNorm (reference backbone.py:125-126, `--norm_layer_backbone batchnorm`): torch's module and state_dict (weight, bias,
+    running_mean, running_var, num_batches_tracked), never run through torch.  In eval mode its running statistics fold into the
+    producing convolution's epilogue like FrozenBatchNorm2d's (`affine`); in training mode `act` normalises with the batch statistics
+    and updates the running ones (`Fn.BatchNormAct`, csrc/bnorm.hip) -- whatever `requires_grad` says and also under no_grad, as
+    nn.BatchNorm2d does."""
+
+    def __init__(self, n):
+        super().__init__(n)                 # affine = True, track_running_stats = True, eps = 1e-5, momentum = 0.1
+        del self.__dict__['affine']         # torch's flag (always True here) would hide the method every norm layer of the body has
+
+    def extra_repr(self):
+        return f'{self.num_features}, eps={self.eps}, momentum={self.momentum}'
+
+    def affine(self):
+        return _prep.bn_affine(self.weight, self.bias, self.running_mean, self.running_var, self.eps, frozen=False)
+
+    def act(self, z, residual=None, relu=False):
+        """Training mode: act(BatchNorm(z) (+ residual)) on the batch statistics; one more batch tracked."""
+        self.num_batches_tracked += 1
+        return Fn.BatchNormAct.apply(z, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum, residual,
+                                     relu)
+
+
+def _live(norm):
+    return isinstance(norm, BatchNorm2d)
+
+
+def _grad_asked(mod, x):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in mod.parameters()))
+
+
+def _refuse_eval_grad(what):
+    raise NotImplementedError(f'{what} with live BatchNorm in eval mode has no backward pass (the fused eval kernels have no gradient for '
+                              'the weight and bias of the norm): call .train() on the model to train through it, or run it under '
+                              'torch.no_grad()')
+
+
 class _Bottleneck(nn.Module):
-    """ResNet v1.5 bottleneck (stride on the 3x3)."""
+    """ResNet v1.5 bottleneck (stride on the 3x3).  With live BatchNorm in training mode the block is a chain of tape nodes: the three
+    convolutions without epilogue (`Fn.conv`), each followed by `Fn.BatchNormAct` (the last one with the shortcut and the ReLU)."""
 
     def __init__(self, inplanes, planes, stride, downsample, norm_layer):
         super().__init__()
@@ -81,7 +122,17 @@ class _Bottleneck(nn.Module):
         # set by _ResNetBody: is the input a ReLU output / does the output feed anything besides the next block
         self.mask_input, self.mask_gy = False, True
 
+    def forward_live(self, x):
+        o = self.bn1.act(Fn.conv(x, self.conv1.weight), relu=True)
+        o = self.bn2.act(Fn.conv(o, self.conv2.weight, kh=3, kw=3, stride=self.stride, pad=1), relu=True)
+        return _live_tail(self, x, o)
+
     def forward(self, x):
+        if _live(self.bn1):
+            if self.training:
+                return self.forward_live(x)
+            if _grad_asked(self, x):
+                _refuse_eval_grad('a ResNet block')
         if torch.is_grad_enabled() and x.dim() == 4 and self.conv1.weight.shape[0] % 32 == 0:
             ds = self.downsample
             sd, bd = ds[1].affine() if ds is not None else (None, None)
@@ -105,6 +156,15 @@ class _Bottleneck(nn.Module):
         return Fn.conv(o, self.conv3.weight, scale=s, shift=b, residual=idt, act=ops.ACT_RELU)
 
 
+def _live_tail(blk, x, o):
+    """conv3 -> bn3 (+ shortcut, ReLU) of a live-BatchNorm block; the projection shortcut is a convolution and a norm without ReLU."""
+    if blk.downsample is not None:
+        idt = blk.downsample[1].act(Fn.conv(x, blk.downsample[0].weight, stride=blk.stride))
+    else:
+        idt = x
+    return blk.bn3.act(Fn.conv(o, blk.conv3.weight), residual=idt, relu=True)
+
+
 class _GroupedBottleneck(nn.Module):
     """ResNeXt bottleneck (torchvision's `Bottleneck` with groups > 1; same module / state_dict names): 1x1 to `width` =
     int(planes * base_width / 64) * groups channels, GROUPED 3x3 (stride on it) through `ops.gconv3x3` with bn2 + ReLU in its epilogue,
@@ -126,7 +186,14 @@ class _GroupedBottleneck(nn.Module):
         self.mask_input, self.mask_gy = False, True           # (set by _ResNetBody; only Fn.Bottleneck reads them)
 
     def forward(self, x):
-        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        grad = _grad_asked(self, x)
+        if _live(self.bn1):
+            if self.training:         # the bare grouped convolution (no affine, no ReLU, no mask) between the norms
+                o = self.bn1.act(Fn.conv(x, self.conv1.weight), relu=True)
+                o = self.bn2.act(Fn.GConv3x3.apply(o, self.conv2.weight, None, None, self.groups, self.stride, False), relu=True)
+                return _live_tail(self, x, o)
+            if grad:
+                _refuse_eval_grad('a ResNeXt block')
         if grad and not self.training:
             raise NotImplementedError('a ResNeXt block in eval mode has no backward pass: call .train() on the model to train through it '
                                       '(FrozenBN makes the two modes compute the same), or train with --lr_backbone 0 (a frozen '
@@ -179,11 +246,20 @@ class _ResNetBody(nn.Module):
 
     def forward(self, x, init_conv=None):
         """x: NHWC image; with `init_conv` (1 -> 3 channels) the stem is ONE differentiable op (Fn.Stem)."""
-        s, b = self.bn1.affine()
-        if init_conv is not None:
-            x = Fn.Stem.apply(x, init_conv.weight, init_conv.bias, self.conv1.weight, s, b)
+        if _live(self.bn1) and self.training:
+            # live BatchNorm: the bare stem (Fn.StemRaw: the stem kernel has the ReLU built in), then the norm + ReLU
+            z = Fn.StemRaw.apply(x, init_conv.weight, init_conv.bias, self.conv1.weight) if init_conv is not None else \
+                Fn.conv(x, self.conv1.weight, kh=7, kw=7, stride=2, pad=3)
+            x = self.bn1.act(z, relu=True)
         else:
-            x = Fn.conv(x, self.conv1.weight, scale=s, shift=b, kh=7, kw=7, stride=2, pad=3, act=ops.ACT_RELU)
+            if _live(self.bn1) and torch.is_grad_enabled() and (x.requires_grad or self.conv1.weight.requires_grad or
+                                                                self.bn1.weight.requires_grad):
+                _refuse_eval_grad('the stem')
+            s, b = self.bn1.affine()
+            if init_conv is not None:
+                x = Fn.Stem.apply(x, init_conv.weight, init_conv.bias, self.conv1.weight, s, b)
+            else:
+                x = Fn.conv(x, self.conv1.weight, scale=s, shift=b, kh=7, kw=7, stride=2, pad=3, act=ops.ACT_RELU)
         taps = [x]
         x = Fn.MaxPool.apply(x, True)              # the stem output is a ReLU output
         for li in range(1, 5):
@@ -298,14 +374,17 @@ class BackboneBase(nn.Module):
 
 
 class Backbone(BackboneBase):
-    """ResNet / ResNeXt / EfficientNet backbone with frozen BatchNorm (reference backbone.py:116-132)."""
+    """ResNet / ResNeXt / EfficientNet backbone (reference backbone.py:116-132); `norm_layer_name`: frozen_batchnorm, or batchnorm
+    (live `BatchNorm2d`) for the ResNet and ResNeXt names."""
 
     def __init__(self, name, in_channels, train_backbone, dilation, norm_layer_name):
         if name not in _RESNET_LAYERS and name not in _RESNEXT and name not in _EFFICIENTNET:
             raise ValueError(f'not supported {name}: the accelerated path implements '
                              f'{sorted(_RESNET_LAYERS) + sorted(_RESNEXT) + sorted(_EFFICIENTNET)} (efficientnet_v2_* and vgg16_bn are not)')
-        if norm_layer_name != 'frozen_batchnorm':
-            raise NotImplementedError('only --norm_layer_backbone frozen_batchnorm (reference default) is implemented')
+        if norm_layer_name not in ('frozen_batchnorm', 'batchnorm') or (name in _EFFICIENTNET and norm_layer_name != 'frozen_batchnorm'):
+            raise NotImplementedError('only --norm_layer_backbone frozen_batchnorm (reference default) is implemented' if name in _EFFICIENTNET
+                                      else f'--norm_layer_backbone {norm_layer_name}: frozen_batchnorm (reference default) and batchnorm are '
+                                      'implemented')
         if name in _EFFICIENTNET:
             if train_backbone:
                 raise NotImplementedError(f'fine-tuning the {name} body is not implemented (the depthwise and squeeze-and-excitation kernels '
@@ -318,7 +397,8 @@ class Backbone(BackboneBase):
             self.init_conv.requires_grad_(False)
             return
         layers, groups, base_width = _RESNEXT[name] if name in _RESNEXT else (_RESNET_LAYERS[name], 1, 64)
-        super().__init__(_ResNetBody(layers, FrozenBatchNorm2d, dilation=dilation, groups=groups, base_width=base_width), name,
+        norm_layer = BatchNorm2d if norm_layer_name == 'batchnorm' else FrozenBatchNorm2d
+        super().__init__(_ResNetBody(layers, norm_layer, dilation=dilation, groups=groups, base_width=base_width), name,
                          in_channels, train_backbone)
         if groups > 1 and not train_backbone and hasattr(self, 'init_conv'):
             # a frozen ResNeXt body asks for no gradient, so none reaches init_conv; its learning rate is --lr_backbone = 0 anyway

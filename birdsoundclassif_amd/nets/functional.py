@@ -555,10 +555,12 @@ class GConv3x3(Function):
     `ops.gconv3x3_wgrad`, each only when its gradient is asked for; both apply the ReLU mask (y > 0) and the scale themselves."""
 
     @staticmethod
-    def forward(ctx, x, weight, scale, shift, groups, stride):
-        y = ops.gconv3x3(x, _prep.gconv(weight, groups), groups, stride=stride, scale=scale, shift=shift, relu=True)
+    def forward(ctx, x, weight, scale, shift, groups, stride, relu=True):
+        """`relu` = False (with scale = shift = None): the bare grouped convolution in front of a live BatchNorm (`BatchNormAct`); the
+        gradient kernels then run without mask and scale."""
+        y = ops.gconv3x3(x, _prep.gconv(weight, groups), groups, stride=stride, scale=scale, shift=shift, relu=relu)
         ctx.cfg = (groups, stride)
-        ctx.save_for_backward(x, weight, scale, y)
+        ctx.save_for_backward(x, weight, scale, y if relu else None)
         return y
 
     @staticmethod
@@ -578,7 +580,7 @@ class GConv3x3(Function):
                 sink[1]()
             else:
                 gw = ops.gconv3x3_wgrad(gy, x, groups, stride=stride, scale=scale, y=y, channels=C_)
-        return gx, gw, None, None, None, None
+        return gx, gw, None, None, None, None, None
 
 
 def conv(x, weight, bias=None, scale=None, shift=None, residual=None, kh=1, kw=1, stride=1, pad=0, act=ACT_NONE, alpha=1.0,
@@ -941,6 +943,62 @@ class BatchNormTrain(Function):
         C_ = x.shape[-1]
         gx, gw, gb = ops.bn_train_bwd(gy.contiguous().view(-1, C_), x.view(-1, C_), mean, invstd, weight.detach())
         return gx.view(x.shape), gw, gb, None, None, None, None
+
+
+class BatchNormAct(Function):
+    """y = act(BatchNorm_train(z) (+ residual)): the live BatchNorm of a backbone bottleneck with the add and the ReLU behind it
+    (`ops.bn_act_train_fwd` / `ops.bn_act_train_bwd`, csrc/bnorm.hip); running statistics updated in place.  The node masks the incoming
+    gradient by (y > 0) itself, always: it takes no part in the `_STASH` / `_PREMASKED` hand-overs (a gradient that a consumer already
+    masked is masked again, which changes nothing)."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, run_mean, run_var, eps, momentum, residual=None, relu=False):
+        C_ = z.shape[-1]
+        y, mean, invstd = ops.bn_act_train_fwd(z.view(-1, C_), weight.detach(), bias.detach(), eps, momentum, run_mean, run_var,
+                                               residual=residual.view(-1, C_) if residual is not None else None, relu=relu)
+        _prep.bump()                       # running statistics changed behind torch's back
+        ctx.relu, ctx.has_res = bool(relu), residual is not None
+        ctx.save_for_backward(z, weight, y if relu else None, mean, invstd)
+        return y.view(z.shape)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        z, weight, y, mean, invstd = ctx.saved_tensors
+        C_ = z.shape[-1]
+        gy = gy.contiguous()
+        want_res = ctx.has_res and ctx.needs_input_grad[7]
+        gz, gw, gb, gres = ops.bn_act_train_bwd(gy.view(-1, C_), y.view(-1, C_) if ctx.relu else None, z.view(-1, C_), mean, invstd,
+                                                weight.detach(), relu=ctx.relu, want_gres=want_res and ctx.relu)
+        if want_res:                       # without ReLU the residual's gradient is gy itself: nothing is written
+            gres = gres.view(z.shape) if ctx.relu else gy
+        return gz.view(z.shape), gw, gb, None, None, None, None, gres if want_res else None, None
+
+
+class StemRaw(Function):
+    """init_conv (1 -> 3, 1x1 + bias) followed by conv1 7x7 / 2 WITHOUT norm or ReLU: the stem in front of a live BatchNorm
+    (`BatchNormAct`).  Forward: `ops.init_conv` then the general implicit GEMM (`ops.conv2d`, as EfficientNet's 3-channel stem).
+    Backward: the formulas of `Stem.backward` with scale = 1 on the incoming gradient (`ops.stem7x7_wgrad`)."""
+
+    @staticmethod
+    def forward(ctx, x, w_init, b_init, w1):
+        B, H, W = x.shape[:3]
+        img3 = ops.init_conv(x.view(B, H, W, 1), w_init.detach(), b_init.detach())
+        y = ops.conv2d(img3, _prep.krsc(w1), 7, 7, 2, 3)
+        ctx.save_for_backward(x, w_init, b_init, w1)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, w_init, b_init, w1 = ctx.saved_tensors
+        U, V = ops.stem7x7_wgrad(x, gy.contiguous())
+        wi, bi = w_init.detach().view(3), b_init.detach().view(3)
+        gw1 = wi.view(1, 3, 1, 1) * U[:, None] + bi.view(1, 3, 1, 1) * V[:, None]
+        w1d = w1.detach()
+        gwi = (w1d * U[:, None]).sum(dim=(0, 2, 3)).view_as(w_init)
+        gbi = (w1d * V[:, None]).sum(dim=(0, 2, 3))
+        return None, gwi, gbi, gw1
 
 
 class PairSoftmax(Function):

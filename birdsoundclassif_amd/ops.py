@@ -1613,6 +1613,65 @@ def bn_train_bwd(g2d, x2d, mean, invstd, w):
     return gx, gw, gb
 
 
+def bn_act_plan(M, C_):
+    """Host-only (no GPU needed): (partial-sum slots, workspace bytes) of `bn_act_train_fwd` / `bn_act_train_bwd` on [M, C] rows -- a
+    function of (M, C) alone (nbm_bn_act_plan)."""
+    parts, nbytes = C.c_int(0), C.c_int64(0)
+    check(lib().nbm_bn_act_plan(int(M), int(C_), C.byref(parts), C.byref(nbytes)), 'nbm_bn_act_plan')
+    return parts.value, nbytes.value
+
+
+def _bn_act_workspace(M, C_, workspace, device):
+    nbytes = bn_act_plan(M, C_)[1]
+    if workspace is None:          # its previous contents are never read
+        return torch.empty((nbytes,), device=device, dtype=torch.uint8), nbytes
+    if not (workspace.is_cuda and workspace.is_contiguous() and workspace.numel() * workspace.element_size() >= nbytes):
+        raise ValueError(f'bn_act: the workspace must be a contiguous device tensor of at least {nbytes} bytes')
+    return workspace, nbytes
+
+
+def bn_act_train_fwd(z2d, gamma, beta, eps, momentum, run_mean=None, run_var=None, residual=None, relu=False, workspace=None):
+    """nn.BatchNorm2d in training mode over rows z2d [M, C] (+ residual [M, C]) (+ ReLU) -> (y, mean, invstd); the running statistics
+    (both or neither) are updated in place (csrc/bnorm.hip)."""
+    M, C_ = z2d.shape
+    ws, nbytes = _bn_act_workspace(M, C_, workspace, z2d.device)
+    mean = torch.empty((C_,), device=z2d.device, dtype=torch.float32)
+    invstd = torch.empty_like(mean)
+    y = torch.empty_like(z2d)
+    if residual is not None and _chk(residual, name='residual').shape != z2d.shape:
+        raise ValueError('bn_act_train_fwd: the residual must have the shape of z')
+    for t, nm in ((gamma, 'gamma'), (beta, 'beta'), (run_mean, 'run_mean'), (run_var, 'run_var')):
+        if t is not None and _chk(t, name=nm).numel() != C_:
+            raise ValueError(f'bn_act_train_fwd: {nm} must hold {C_} values')
+    check(lib().nbm_bn_act_train_fwd(_ptr(_chk(z2d, name='z')), M, C_, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
+                                     _ptr(run_mean), _ptr(run_var), _ptr(residual), int(bool(relu)), _ptr(ws), nbytes, _ptr(mean),
+                                     _ptr(invstd), _ptr(y), _stream()), 'nbm_bn_act_train_fwd')
+    return y, mean, invstd
+
+
+def bn_act_train_bwd(gy2d, y2d, z2d, mean, invstd, gamma, relu=False, want_gres=False, workspace=None):
+    """Gradients of `bn_act_train_fwd` -> (gz, ggamma, gbeta, gres or None).  `y2d`: the forward output (the ReLU mask; None without
+    relu); `want_gres`: also write the masked gradient, which is the residual's."""
+    M, C_ = z2d.shape
+    ws, nbytes = _bn_act_workspace(M, C_, workspace, z2d.device)
+    if relu and y2d is None:
+        raise ValueError('bn_act_train_bwd: relu needs the forward output y')
+    for t, nm in ((gy2d, 'gy'), (y2d, 'y')):
+        if t is not None and _chk(t, name=nm).shape != z2d.shape:
+            raise ValueError(f'bn_act_train_bwd: {nm} must have the shape of z')
+    for t, nm in ((mean, 'mean'), (invstd, 'invstd'), (gamma, 'gamma')):
+        if _chk(t, name=nm).numel() != C_:
+            raise ValueError(f'bn_act_train_bwd: {nm} must hold {C_} values')
+    gz = torch.empty_like(z2d)
+    gw = torch.empty((C_,), device=z2d.device, dtype=torch.float32)
+    gb = torch.empty_like(gw)
+    gres = torch.empty_like(z2d) if want_gres else None
+    check(lib().nbm_bn_act_train_bwd(_ptr(gy2d), _ptr(y2d if relu else None), _ptr(_chk(z2d, name='z')), M, C_, _ptr(mean), _ptr(invstd),
+                                     _ptr(gamma), int(bool(relu)), _ptr(ws), nbytes, _ptr(gz), _ptr(gw), _ptr(gb), _ptr(gres),
+                                     _stream()), 'nbm_bn_act_train_bwd')
+    return gz, gw, gb, gres
+
+
 def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None):
     """gpool [B*R,ph,pw,C] -> list of zero-initialised-then-accumulated gradient maps (NHWC) for the FPN levels.
     `pooled` {level index: stride of the RPN's depthwise convolution on that map}: those maps come from the persistent pool of

@@ -810,6 +810,30 @@ int nbm_bn_train_fwd(const float* x, int64_t M, int C, const float* w, const flo
                      float* run_mean, float* run_var, double* stats_ws, float* mean, float* invstd, float* y, void* stream);
 int nbm_bn_train_bwd(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd,
                      const float* w, double* red_ws, float* gx, float* gw, float* gb, void* stream);
+/* ---- live BatchNorm of the backbone (csrc/bnorm.hip): nn.BatchNorm2d in training mode over rows [M][C] (NHWC, M = B*H*W), with
+ * the residual add and the ReLU that follow it in a bottleneck in the same passes:
+ *   forward : mean[c], invstd[c] = batch statistics (biased variance), y = act((z - mean) * invstd * gamma + beta (+ residual)),
+ *             act = ReLU when `relu`; run_mean / run_var (both or neither) <- (1 - momentum) * old + momentum * new, the variance
+ *             unbiased (M / (M - 1)) for M > 1.  Two passes over z (reduce, apply) and one write of y.
+ *   backward: g' = gy * (y > 0) with `relu` (y: the forward output; may be NULL without relu), else g' = gy;
+ *             gbeta = sum g', ggamma = sum g' * xhat, gz = gamma * invstd * (g' - gbeta / M - xhat * ggamma / M),
+ *             gres (optional) = g'.  Two passes over (gy, y, z).
+ * Every sum is carried in double: one partial per workgroup, stored to a slot of `workspace`, and a finish kernel sums the slots in a
+ * fixed ascending order.  No atomics, no zero fill: the previous contents of `workspace` are never read, two runs give the same
+ * bits.  nbm_bn_act_plan: host only, no HIP call; *parts = the number of slots, *workspace_bytes = what both calls need, functions of
+ * (M, C) alone.  All offsets are 64-bit; every global access of the streaming kernels is a 16-byte access.
+ * C % 4 != 0: NBM_EUNSUPPORTED; a pointer that is not 16-byte aligned: NBM_EALIGN; M < 1, C < 1, a missing pointer, a workspace
+ * smaller than the plan's: NBM_EINVAL.  Nothing is launched then.
+ *
+ * Replaces: `nn.BatchNorm2d` as the body's norm layer, reference backbone.py:125-126 (`--norm_layer_backbone batchnorm`), with the
+ *   ReLU / `out += identity` of torchvision's Bottleneck behind it, and what autograd derives for them (train.py:212). */
+int nbm_bn_act_plan(int64_t M, int C, int* parts, int64_t* workspace_bytes);
+int nbm_bn_act_train_fwd(const float* z, int64_t M, int C, const float* gamma, const float* beta, float eps, float momentum,
+                         float* run_mean, float* run_var, const float* residual, int relu, void* workspace, int64_t workspace_bytes,
+                         float* mean, float* invstd, float* y, void* stream);
+int nbm_bn_act_train_bwd(const float* gy, const float* y, const float* z, int64_t M, int C, const float* mean, const float* invstd,
+                         const float* gamma, int relu, void* workspace, int64_t workspace_bytes, float* gz, float* ggamma,
+                         float* gbeta, float* gres, void* stream);
 /* ROIPooling backward at any pool size (autograd of layers.py:406-497 with --roi_pool_h / --roi_pool_w): scatter-add of
  * gpool [B*n_roi][pool_h][pool_w][C] into the given gradient maps, windows and bins of nbm_roi_pool_hw on the levels in
  * `level`.  The sums are fp32 atomics: RoI windows overlap, so their order -- and the last bits of the result -- is not fixed.
