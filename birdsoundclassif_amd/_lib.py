@@ -93,7 +93,7 @@ class GemmPlan(C.Structure):
                 ('plain', C.c_int), ('b_generic', C.c_int), ('narrow_m', C.c_int), ('halves', C.c_int)]
 
 
-_P, _I, _L, _F, _U64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
+_P, _I, _L, _F, _U64, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
 # name -> argtypes (restype is int unless noted); must list every symbol of include/nbm_hip.h
 SIGNATURES = {
@@ -157,6 +157,11 @@ SIGNATURES = {
     'nbm_leaky_relu_bwd': [_P, _P, _P, _F, _L, _P],
     'nbm_layernorm_bwd': [_P, _P, _P, _L, _I, _F, _P, _P, _P, _P],
     'nbm_mha_small_bwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _L, _L, _P, _F, _P],
+    'nbm_layernorm_bwd_det': [_P, _P, _P, _L, _I, _F, _P, _P, _P, _P, _L, _P],
+    'nbm_dropout': [_P, _P, _P, _L, _U32, _F, _U64, _U32, _U32, _P],
+    'nbm_mha_small_drop': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _L, _L, _P, _F, _U32, _F, _U64, _U32, _U32, _P],
+    'nbm_mha_small_drop_bwd': [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _L, _L, _P, _F,
+                               _U32, _F, _U64, _U32, _U32, _P],
     'nbm_zero_roi_windows': [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P],
     'nbm_zero_pattern': [_P, _I, _I, _I, _I, _I, _P],
     'nbm_zero_tiles': [_P, _I, _I, _I, _I, _P, _I, _P, _P],

@@ -703,6 +703,61 @@ class MhaSmall(Function):
         return gq, gk, gv, None, None, None, None, None, None
 
 
+class LayerNormDet(Function):
+    """`LayerNorm` whose weight / bias gradients are summed in a fixed order (the dropout path: a (seed, call) pair reproduces
+    its gradients bit for bit); forward and d/dx are those of `LayerNorm`."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        ctx.save_for_backward(x, weight)
+        ctx.eps = eps
+        return ops.layernorm(x, weight.detach(), bias.detach(), eps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, weight = ctx.saved_tensors
+        gx, gw, gb = ops.layernorm_bwd_det(x, weight.detach(), g.contiguous(), ctx.eps)
+        return gx, gw, gb, None
+
+
+class MhaSmallDrop(Function):
+    """`MhaSmall` with dropout on the probabilities (nn.MultiheadAttention(dropout=p) in training mode); the mask is a function of
+    (seed, call, site_id) and is evaluated again in the backward kernels, like the probabilities."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid, p, seed, call, site_id):
+        ctx.save_for_backward(q, k, v, n_valid)
+        ctx.geom = (S, N, nhead, seq_stride, batch_stride)
+        ctx.drop = (p, seed, call, site_id)
+        return ops.mha_small_drop(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid, p, seed, call, site_id)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go):
+        q, k, v, n_valid = ctx.saved_tensors
+        gq, gk, gv = ops.mha_small_drop_bwd(q, k, v, go.contiguous(), *ctx.geom, n_valid, *ctx.drop)
+        return (gq, gk, gv) + (None,) * 10
+
+
+class Dropout(Function):
+    """residual + dropout(x) (residual may be None) with the mask of `ops.dropout_keep_reference(seed, call, site, x.numel(), p)`:
+    nn.Dropout in training mode and the residual addition behind it.  Nothing is saved: the backward pass is the same kernel on
+    the gradient, and the residual branch passes the gradient through."""
+
+    @staticmethod
+    def forward(ctx, x, residual, p, seed, call, site):
+        ctx.drop = (p, seed, call, site)
+        return ops.dropout(x.contiguous(), p, seed, call, site, residual=residual.contiguous() if residual is not None else None)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        g = g.contiguous()
+        gx = ops.dropout(g, *ctx.drop) if ctx.needs_input_grad[0] else None
+        return gx, (g if ctx.needs_input_grad[1] else None), None, None, None, None
+
+
 class Stem(Function):
     """init_conv (1 -> 3, 1x1 + bias) followed by conv1 7x7/s2 + FrozenBN + ReLU (reference backbone.py:104-113 and
     torchvision's stem).  Backward never forms the 3-channel data gradient: with U[n,t] = sum_m g[m,n] x[pix(m)+t] and

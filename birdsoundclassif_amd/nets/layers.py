@@ -314,7 +314,13 @@ class Transformer_RCNN(nn.Module):
     """reference layers.py:589-651 (`--tf_rcnn`).  Default flavour: post-norm ReLU encoder fed
     rois_embed + pos_embed with batch_first=False, i.e. the reference attends ACROSS THE IMAGES OF THE BATCH for each RoI
     slot (sequence axis = bs, <= 128 here); `tf_pe_qk`: DETR flavour, attention across the RoIs of one image with
-    q = k = src + pos and LeakyReLU.  Dropout is inactive in both (eval)."""
+    q = k = src + pos and LeakyReLU.
+    `--dropout p` (0 <= p < 1): in training mode both flavours drop at four sites per encoder layer -- the attention probabilities,
+    dropout1 behind out_proj, the feed-forward's dropout behind its activation, dropout2 behind linear2 (reference
+    self_attention.py:113-135; nn.TransformerEncoderLayer) -- with masks that are a function of (seed, call, 4 * layer + site,
+    element index): `ops.dropout_keep_reference`.  `seed` is torch.initial_seed() at the first training-mode forward, `call` counts
+    those forwards; both are plain attributes (no buffers: the state_dict is that of dropout 0), so a resumed run starts its
+    stream again.  In evaluation mode p has no effect."""
 
     def __init__(self, config):
         super().__init__()
@@ -322,8 +328,9 @@ class Transformer_RCNN(nn.Module):
         in_dim = config.out_fpn_chan * config.roi_pool_h * config.roi_pool_w
         E = config.tf_model_dim
         self.tf_pe_qk = config.tf_pe_qk
-        if getattr(config, 'dropout', 0):
-            raise NotImplementedError('Transformer_RCNN: dropout > 0 is not implemented')
+        self.dropout_p = float(getattr(config, 'dropout', 0) or 0)
+        ops.dropout_params(self.dropout_p)            # ValueError unless 0 <= --dropout < 1
+        self.dropout_seed, self.dropout_call = None, 0
         if not self.tf_pe_qk and E != 512:
             raise ValueError('the reference hard-codes d_model=512 for the non-pe_qk encoder (layers.py:619)')
         self.nhead = config.tf_nhead
@@ -339,6 +346,10 @@ class Transformer_RCNN(nn.Module):
             if p.dim() > 1:
                 nn.init.xavier_uniform_(p)
 
+    def set_dropout_stream(self, seed, call=0):
+        """Fix the dropout stream: the next training-mode forward uses the masks of (seed, call), the one after it (seed, call + 1)."""
+        self.dropout_seed, self.dropout_call = int(seed) & 0xffffffffffffffff, int(call)
+
     def forward_nhwc(self, pool, pe, B, R, n_valid=None, segments=None):
         """pool, pe: NHWC [B*R,ph,pw,C]; n_valid: device int32, element 0 = RoIs per image that are real
         (the same count for every image of one model call; pe_qk masks the rest)
@@ -347,7 +358,8 @@ class Transformer_RCNN(nn.Module):
         a count per image (int32 [B], equal within a segment): the attention runs through `ops.mha_segments`, whose valid
         rows are those of a call on the segment alone bit for bit; rows that are no RoI come out as finite numbers that
         `ops.rcnn_post` never reads."""
-        if torch.is_grad_enabled() and (self.training or pool.requires_grad):
+        dropping = self.training and self.dropout_p > 0       # active iff training, like nn.Dropout -- also under no_grad
+        if dropping or (torch.is_grad_enabled() and (self.training or pool.requires_grad)):
             if segments is not None:
                 raise NotImplementedError('Transformer_RCNN: a segmented batch is an evaluation geometry (no backward form)')
             return self._forward_train(pool, pe, B, R, n_valid)
@@ -397,7 +409,13 @@ class Transformer_RCNN(nn.Module):
         else:
             x = Fn.Add.apply(x, pos)
             geom, ff_act = (B, R, self.nhead, R, 1, None), Fn.ACT_RELU
-        for l in self.encoder.layers:
+        p = self.dropout_p if self.training else 0.0
+        if p > 0:
+            if self.dropout_seed is None:
+                self.dropout_seed = torch.initial_seed() & 0xffffffffffffffff
+            seed, call = self.dropout_seed, self.dropout_call
+            self.dropout_call += 1
+        for li, l in enumerate(self.encoder.layers):
             w, b = l.self_attn.in_proj_weight, l.self_attn.in_proj_bias
             if self.tf_pe_qk:
                 qk = Fn.linear(Fn.Add.apply(x, pos), w[:2 * E], b[:2 * E])
@@ -405,6 +423,14 @@ class Transformer_RCNN(nn.Module):
             else:
                 qkv = Fn.linear(x, w, b)
                 q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+            if p > 0:       # the four dropout sites of the layer; the residual additions move from the GEMM epilogues into Fn.Dropout
+                a = Fn.MhaSmallDrop.apply(q, k, v, *geom, p, seed, call, 4 * li)
+                a = Fn.linear(a, l.self_attn.out_proj.weight, l.self_attn.out_proj.bias)
+                x = Fn.LayerNormDet.apply(Fn.Dropout.apply(a, x, p, seed, call, 4 * li + 1), l.norm1.weight, l.norm1.bias, l.norm1.eps)
+                h = Fn.Dropout.apply(Fn.linear(x, l.linear1.weight, l.linear1.bias, act=ff_act), None, p, seed, call, 4 * li + 2)
+                h = Fn.linear(h, l.linear2.weight, l.linear2.bias)
+                x = Fn.LayerNormDet.apply(Fn.Dropout.apply(h, x, p, seed, call, 4 * li + 3), l.norm2.weight, l.norm2.bias, l.norm2.eps)
+                continue
             a = Fn.MhaSmall.apply(q, k, v, *geom)
             x = Fn.LayerNorm.apply(Fn.linear(a, l.self_attn.out_proj.weight, l.self_attn.out_proj.bias, residual=x),
                                    l.norm1.weight, l.norm1.bias, l.norm1.eps)

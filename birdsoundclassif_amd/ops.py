@@ -827,6 +827,105 @@ def mha_segments(q, k, v, R, nhead, mode, segments, n_roi, max_count=None):
     return out
 
 
+# --------------------------------------------------------------------------- dropout (Transformer_RCNN head, training mode)
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 in NumPy (host only): `counter` four and `key` two uint32 values or arrays of one shape -> uint32 [..., 4].
+    csrc/nbm_philox.h is the same function on the device."""
+    import numpy as np
+    c = [np.asarray(v).astype(np.uint64) for v in counter]
+    k = [np.asarray(v).astype(np.uint64) for v in key]
+    lo32 = np.uint64(0xffffffff)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M0) * c[0], np.uint64(_PHILOX_M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & lo32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & lo32]
+        k = [(k[0] + np.uint64(_PHILOX_W0)) & lo32, (k[1] + np.uint64(_PHILOX_W1)) & lo32]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def dropout_params(p):
+    """-> (threshold, scale): an element is kept iff its mask word >= threshold = round(p * 2^32) (as a uint32), and a kept element
+    is multiplied by scale = float32(1) / float32(1 - p).  0 <= p < 1."""
+    import numpy as np
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f'--dropout must lie in [0, 1), got {p}')
+    return min(int(round(p * 2.0 ** 32)), 0xffffffff), float(np.float32(1) / np.float32(1.0 - p))
+
+
+def dropout_keep_reference(seed, call, site_id, n, p):
+    """The dropout mask as a specification (host only, NumPy; no library call): bool [n], element i is kept iff output word i & 3 of
+    Philox4x32-10 at counter (q & 0xffffffff, q >> 32, site_id, call), q = i >> 2, key = (low, high) half of the 64-bit `seed`, is
+    >= round(p * 2^32).  The kernels (`dropout`, `mha_small_drop`) agree with it bit for bit."""
+    import numpy as np
+    threshold, _ = dropout_params(p)
+    seed = int(seed) & 0xffffffffffffffff
+    q = np.arange((int(n) + 3) // 4, dtype=np.uint64)
+    words = philox4x32_10((q & np.uint64(0xffffffff), q >> np.uint64(32), int(site_id) & 0xffffffff, int(call) & 0xffffffff),
+                          (seed & 0xffffffff, seed >> 32))
+    return words.reshape(-1)[:int(n)] >= np.uint32(threshold)
+
+
+def _drop_args(p, seed, call, site_id):
+    threshold, scale = dropout_params(p)
+    return (C.c_uint32(threshold), C.c_float(scale), C.c_uint64(int(seed) & 0xffffffffffffffff), C.c_uint32(int(call) & 0xffffffff),
+            C.c_uint32(int(site_id) & 0xffffffff))
+
+
+def dropout(x, p, seed, call, site_id, residual=None):
+    """y = (residual or 0) + where(keep, x * scale, 0) with the mask of `dropout_keep_reference(seed, call, site_id, x.numel(), p)`
+    over x's elements in memory order; each product and sum is one float32 operation.  With residual=None it is also its own
+    backward pass (x = the incoming gradient)."""
+    _chk(x, name='x')
+    if residual is not None and _chk(residual, name='residual').shape != x.shape:
+        raise ValueError(f'dropout: residual {tuple(residual.shape)} does not match x {tuple(x.shape)}')
+    y = torch.empty_like(x)
+    check(lib().nbm_dropout(_ptr(x), _ptr(residual), _ptr(y), x.numel(), *_drop_args(p, seed, call, site_id), _stream()),
+          'nbm_dropout')
+    return y
+
+
+def mha_small_drop(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid, p, seed, call, site_id):
+    """`mha_small` with dropout on the softmax probabilities: the mask is `dropout_keep_reference(seed, call, site_id,
+    N * nhead * S * S, p)` read as a dense [N, nhead, S, S] tensor (query row, key column)."""
+    E = q.shape[1]
+    hd = E // nhead
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.stride(1) == 1 and t.is_cuda and t.dtype == torch.float32
+    out = torch.zeros((q.shape[0], E), device=q.device, dtype=torch.float32)
+    check(lib().nbm_mha_small_drop(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(out), E, S, N, nhead,
+                                   hd, seq_stride, batch_stride, _ptr(n_valid), 1.0 / math.sqrt(hd),
+                                   *_drop_args(p, seed, call, site_id), _stream()), 'nbm_mha_small_drop')
+    return out
+
+
+def mha_small_drop_bwd(q, k, v, go, S, N, nhead, seq_stride, batch_stride, n_valid, p, seed, call, site_id):
+    """Gradients of `mha_small_drop` wrt q, k, v (the mask is evaluated again) -> contiguous [S*N, E] each."""
+    E = q.shape[1]
+    hd = E // nhead
+    gq, gk, gv = (torch.zeros((q.shape[0], E), device=q.device, dtype=torch.float32) for _ in range(3))
+    ws = torch.empty((N * nhead, 2, S, S), device=q.device, dtype=torch.float32)
+    go = _chk(go)
+    check(lib().nbm_mha_small_drop_bwd(_ptr(q), _ptr(k), _ptr(v), _ptr(go), q.stride(0), k.stride(0), v.stride(0), go.stride(0),
+                                       _ptr(gq), _ptr(gk), _ptr(gv), E, E, E, _ptr(ws), S, N, nhead, hd, seq_stride, batch_stride,
+                                       _ptr(n_valid), 1.0 / math.sqrt(hd), *_drop_args(p, seed, call, site_id), _stream()),
+          'nbm_mha_small_drop_bwd')
+    return gq, gk, gv
+
+
+def layernorm_bwd_det(x2d, w, g2d, eps=1e-5):
+    """`layernorm_bwd` with gw / gb summed in a fixed order (no atomics): the same inputs give the same bits -> (gx, gw, gb)."""
+    rows, E = x2d.shape
+    gx = torch.empty_like(x2d)
+    gwb = torch.empty((2, E), device=x2d.device, dtype=torch.float32)
+    ws = torch.empty((min((rows + 3) // 4, 256) * 8 * E,), device=x2d.device, dtype=torch.float32)
+    check(lib().nbm_layernorm_bwd_det(_ptr(_chk(x2d)), _ptr(_chk(w)), _ptr(_chk(g2d)), rows, E, float(eps), _ptr(gx), _ptr(gwb[0]),
+                                      _ptr(gwb[1]), _ptr(ws), ws.numel(), _stream()), 'nbm_layernorm_bwd_det')
+    return gx, gwb[0], gwb[1]
+
+
 def pair_softmax(x, n_anchor):
     """x [..., 2*n_anchor] -> softmax over each (bg, fg) pair."""
     _chk(x, name='x')

@@ -781,6 +781,46 @@ int nbm_mha_small_bwd(const float* q, const float* k, const float* v, const floa
                       int go_ld, float* gq, float* gk, float* gv, int gq_ld, int gk_ld, int gv_ld, float* workspace, int S,
                       int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                       float scale, void* stream);
+/* ---- dropout of the Transformer_RCNN head in training mode, `--tf_rcnn --dropout p` (csrc/dropout.hip).  A mask is a pure function
+ * of (seed, call, site_id, element index) -- Philox4x32-10, csrc/nbm_philox.h: counter (q & 0xffffffff, q >> 32, site_id, call) with
+ * q = element index >> 2, key = (low, high) half of `seed`, element i takes output word i & 3 and is kept iff word >= threshold
+ * (threshold = round(p * 2^32)); a kept element is multiplied by `scale` = float32(1) / float32(1 - p), computed by the caller.
+ * Nothing is stored: a backward pass evaluates the same mask again.  ops.dropout_keep_reference (NumPy) states the mask and the
+ * kernels agree with it bit for bit.
+ *
+ * nbm_dropout: y[i] = (residual ? residual[i] : 0) + (keep(i) ? x[i] * scale : 0), i < n, each product and sum rounded to float32 on
+ * its own (no fused multiply-add).  One Philox evaluation and one 16-byte access per four elements, a scalar tail for n % 4.  With
+ * residual == NULL it is also its own backward pass (the incoming gradient takes the place of x); the residual branch passes the
+ * gradient through.  n <= 0 or a missing x / y: NBM_EINVAL; x, y or residual not 16-byte aligned: NBM_EALIGN.
+ * Replaces: `src + self.dropout1(src2)`, `self.dropout(self.activation(...))` and `src + self.dropout2(src2)` of both encoder
+ *   layers in training mode -- self_attention.py:132-135 (`--tf_pe_qk`) and nn.TransformerEncoderLayer (layers.py:619-621) -- and
+ *   what autograd derives for them. */
+int nbm_dropout(const float* x, const float* residual, float* y, int64_t n, uint32_t threshold, float scale, uint64_t seed,
+                uint32_t call, uint32_t site_id, void* stream);
+/* nbm_mha_small with dropout on the softmax probabilities: A[r][j] = keep ? (e_j / sum) * drop_scale : 0, out = A V.  Token layout,
+ * *n_valid handling, limits (S <= 128, hd <= 64) and argument checks are nbm_mha_small's.  The mask element of (batch entry n,
+ * head h, query r, key j) is ((n * nhead + h) * S + r) * S + j -- a dense [N][nhead][S][S] tensor, S the launch's S whatever
+ * *n_valid holds.
+ * Replaces: nn.MultiheadAttention(dropout=p) in training mode, self_attention.py:113,131 / layers.py:619-621. */
+int nbm_mha_small_drop(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
+                       int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
+                       float scale, uint32_t threshold, float drop_scale, uint64_t seed, uint32_t call, uint32_t site_id,
+                       void* stream);
+/* backward of nbm_mha_small_drop (arguments and workspace of nbm_mha_small_bwd): dA = dO V^T, dP = keep ? dA * drop_scale : 0,
+ * dS = P (dP - sum_j P dP), dQ = scale dS K, dK = scale dS^T Q, dV = A^T dO.
+ * Replaces: autograd through nn.MultiheadAttention(dropout=p), train.py:212. */
+int nbm_mha_small_drop_bwd(const float* q, const float* k, const float* v, const float* go, int q_ld, int k_ld, int v_ld,
+                           int go_ld, float* gq, float* gk, float* gv, int gq_ld, int gk_ld, int gv_ld, float* workspace, int S,
+                           int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
+                           float scale, uint32_t threshold, float drop_scale, uint64_t seed, uint32_t call, uint32_t site_id,
+                           void* stream);
+/* nbm_layernorm_bwd with the parameter gradients summed in a fixed order (no atomics; gw, gb are written, not added to): two
+ * calls on the same inputs give the same bits, which the dropout path promises for a (seed, call) pair.  gx holds the bits of
+ * nbm_layernorm_bwd.  workspace: min(ceil(rows / 4), 256) * 8 * E floats or more (previous contents never read); a smaller one,
+ * E > 1024 or a missing pointer: NBM_EINVAL.
+ * Replaces: autograd through norm1 / norm2 of the encoder layers, self_attention.py:133,136 / layers.py:619-621 (train.py:212). */
+int nbm_layernorm_bwd_det(const float* x, const float* w, const float* g, int64_t rows, int E, float eps, float* gx, float* gw,
+                          float* gb, float* workspace, int64_t workspace_floats, void* stream);
 /* gradient of the bilinear (align_corners) up-sampling of fpn.py:143-144 wrt the coarse map [B][Hi][Wi][C], gather form.
  * pattern_stride = S >= 5: the caller guarantees that gy [B][Ho][Wo][C] is zero outside the 5x5 patches around the 3x3 / stride-S /
  * pad-1 pattern (rows and columns o*S - 2 .. o*S + 2): those rows / columns are not read (61 % of the map at S = 8); 0: every
