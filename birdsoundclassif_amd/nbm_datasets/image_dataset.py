@@ -5,7 +5,8 @@ Same constructor, directory layout (`positive_files/<rec>/<rec>__<i>.png` + `ann
 `hard_neg/`), `__len__` and `__getitem__ -> (img, neg_img, bboxes, bird_ids)` as the reference, and the same host RNG
 call order (NumPy global generator: negative choice, gain, 4 coin flips, hard-negative choice, two mix weights, cut-off;
 torch global generator: the noise field), so a seeded run draws what the reference draws.  What changes is where the
-bytes are processed: a worker only inflates the PNG's zlib stream (`raw_item`); `DeviceCollate` ships the filtered
+bytes are processed: a worker only inflates the PNG's zlib stream (`raw_item`; with `device_inflate=True` not even that:
+it ships the stream and `nbm_png_inflate` inflates the batch's streams on the device); `DeviceCollate` ships the filtered
 scanlines of the whole batch to the GPU where `nbm_png_unfilter_gray8`, `nbm_image_half_std_u8` and `nbm_augment_batch`
 reconstruct the pixels and apply the augmentation, producing the `[img, neg_img, bb_coord, bird_ids, lengths]` batch of
 `collate_fn` (nets_utils.py:159-166) with the images already resident in HBM.
@@ -33,9 +34,8 @@ FREQ_ACCURACY = 33.3
 _SIG = b'\x89PNG\r\n\x1a\n'
 
 
-def read_png_scanlines(path):
-    """8-bit greyscale, non-interlaced PNG -> uint8 [H, W+1] filtered scanlines (filter byte + W bytes per line): the
-    host half of `imageio.imread`; the reconstruction runs on the device."""
+def _png_idat(path):
+    """8-bit greyscale, non-interlaced PNG -> (the IDAT chunks' bytes joined: one zlib stream, H, W)."""
     with open(path, 'rb') as f:
         data = f.read()
     if data[:8] != _SIG:
@@ -52,11 +52,28 @@ def read_png_scanlines(path):
         pos += 12 + n
     if hdr is None or hdr[2:] != (8, 0, 0, 0, 0):
         raise NotImplementedError(f'{path}: only 8-bit greyscale non-interlaced PNG is supported (IHDR {hdr})')
-    W, H = hdr[0], hdr[1]
-    raw = np.frombuffer(zlib.decompress(b''.join(parts)), dtype=np.uint8)
+    return b''.join(parts), hdr[1], hdr[0]
+
+
+def read_png_scanlines(path):
+    """8-bit greyscale, non-interlaced PNG -> uint8 [H, W+1] filtered scanlines (filter byte + W bytes per line): the
+    host half of `imageio.imread`; the reconstruction runs on the device."""
+    payload, H, W = _png_idat(path)
+    raw = np.frombuffer(zlib.decompress(payload), dtype=np.uint8)
     if raw.size != H * (W + 1):
         raise ValueError(f'{path}: inflated size {raw.size} != {H}x({W}+1)')
     return raw.reshape(H, W + 1)
+
+
+def read_png_payload(path):
+    """`read_png_scanlines` without the inflate: (payload bytes, H, W) of an 8-bit greyscale, non-interlaced PNG, same
+    refusals.  `nbm_png_inflate` turns a batch of such payloads into the scanlines on the device."""
+    return _png_idat(path)
+
+
+def _geometry(image):
+    """(H, W) of a scanline array or of `read_png_payload`'s tuple."""
+    return image[1:] if isinstance(image, tuple) else (image.shape[0], image.shape[1] - 1)
 
 
 def lowpass_curve(cutting_freq, n_rows):
@@ -82,11 +99,13 @@ def _split_name(png):
 class Img_dataset(Dataset):
     """reference image_dataset.py:13-96."""
 
-    def __init__(self, dataset_path, transform=False, device='cuda', host_noise=True):
+    def __init__(self, dataset_path, transform=False, device='cuda', host_noise=True, device_inflate=False):
         super().__init__()
         self.ds_p = dataset_path
         self.transform = transform
         self.host_noise = host_noise
+        # True: a worker ships the PNG's zlib stream as it is and `nbm_png_inflate` inflates the batch on the device
+        self._read = read_png_payload if device_inflate else read_png_scanlines
         self.positive_files = _listing(dataset_path, 'positive_files')
         self.negative_files = _listing(dataset_path, 'negative_files')
         self.hard_negative_files = _listing(dataset_path, 'hard_neg')
@@ -106,19 +125,20 @@ class Img_dataset(Dataset):
         return self._annot[rec]
 
     def raw_item(self, idx):
-        """Host half of `__getitem__`: file bytes inflated, labels parsed, every random number drawn (reference call
-        order), no pixel touched."""
+        """Host half of `__getitem__`: file bytes inflated (`device_inflate`: only read; 'pos' / 'neg' / 'hard' then hold
+        `read_png_payload`'s (payload, H, W)), labels parsed, every random number drawn (reference call order), no pixel
+        touched."""
         imgp = self.positive_files[idx]
         rec, fileidx = _split_name(imgp)
-        item = {'pos': read_png_scanlines(os.path.join(self.ds_p, 'positive_files', rec, imgp)), 'transform': self.transform}
+        item = {'pos': self._read(os.path.join(self.ds_p, 'positive_files', rec, imgp)), 'transform': self.transform}
         bboxes, bird_ids = self._annotations(rec)[int(fileidx)]
         keep = np.array(bird_ids) != 0                                   # class 0 dropped, image_dataset.py:55-56
         item['bboxes'], item['bird_ids'] = torch.Tensor(bboxes)[keep], torch.Tensor(bird_ids)[keep]
         negp = np.random.choice(self.negative_files, 1)[0]                                            # :59
-        item['neg'] = read_png_scanlines(os.path.join(self.ds_p, 'negative_files', _split_name(negp)[0], negp))
+        item['neg'] = self._read(os.path.join(self.ds_p, 'negative_files', _split_name(negp)[0], negp))
         if not self.transform:
             return item
-        H, W = item['pos'].shape[0], item['pos'].shape[1] - 1
+        H, W = _geometry(item['pos'])
         if self.host_noise:
             item['noise'] = torch.randn((H, W))                                                       # :66
         else:
@@ -128,7 +148,7 @@ class Img_dataset(Dataset):
         item['flags'] = 0
         if flips[0] == 1:
             hardp = np.random.choice(self.hard_negative_files, 1)[0]                                  # :73
-            item['hard'] = read_png_scanlines(os.path.join(self.ds_p, 'hard_neg', _split_name(hardp)[0], hardp))
+            item['hard'] = self._read(os.path.join(self.ds_p, 'hard_neg', _split_name(hardp)[0], hardp))
             item['coef'] = np.random.uniform(0.1, 0.4)                                                # :79
             item['neg_coef'] = np.random.uniform(0.5, 0.99)                                           # :82
             item['flags'] |= 1
@@ -155,14 +175,24 @@ class DeviceCollate:
 
     def __call__(self, items):
         B = len(items)
-        H, W = items[0]['pos'].shape[0], items[0]['pos'].shape[1] - 1
+        H, W = _geometry(items[0]['pos'])
         hard_items = [i for i, it in enumerate(items) if 'hard' in it]
-        raw = self._upload([it['pos'] for it in items] + [it['neg'] for it in items] + [items[i]['hard'] for i in hard_items])
-        n_img = raw.shape[0]
+        images = [it['pos'] for it in items] + [it['neg'] for it in items] + [items[i]['hard'] for i in hard_items]
+        n_img = len(images)
+        device_inflate = isinstance(images[0], tuple)
+        if device_inflate:               # file payloads: inflate on the device into the rows the unfilter kernel reads
+            if any(_geometry(im) != (H, W) for im in images):
+                raise ValueError('all images of a batch must have the same size')
+            packed, table = ops.png_payload_pack([im[0] for im in images])
+            payload = torch.from_numpy(packed).pin_memory().to(self.device, non_blocking=True)
+            status = torch.zeros((1 + n_img,), dtype=torch.int32, device=self.device)     # [0]: filter bytes, then one per stream
+            raw, _ = ops.png_inflate(payload, table, H, W, status=status[1:])
+        else:
+            raw = self._upload(images)
+            status = torch.zeros((1,), dtype=torch.int32, device=self.device)
         pix = torch.empty((n_img, H, W), dtype=torch.uint8, device=self.device)
-        status = torch.zeros((1,), dtype=torch.int32, device=self.device)
         lib, st = ops.lib(), ops._stream()
-        _lib.check(lib.nbm_png_unfilter_gray8(ops._ptr(raw), H * (W + 1), n_img, H, W, ops._ptr(pix), H * W,
+        _lib.check(lib.nbm_png_unfilter_gray8(ops._ptr(raw), raw.stride(0), n_img, H, W, ops._ptr(pix), H * W,
                                               ops._ptr(status), st), 'nbm_png_unfilter_gray8')
         img = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
         neg = torch.empty((B, H, W), dtype=torch.float32, device=self.device)
@@ -194,7 +224,17 @@ class DeviceCollate:
             _lib.check(lib.nbm_augment_batch(ops._ptr(pix), ops._ptr(pix[B:]), ops._ptr(pix[2 * B:]) if hard_items else None,
                                              B, H, W, ops._ptr(prm_dev), ops._ptr(half_std), ops._ptr(noise),
                                              ops._ptr(curve_dev), ops._ptr(img), ops._ptr(neg), st), 'nbm_augment_batch')
-        if int(status.item()):
+        if device_inflate:
+            codes = status.cpu().tolist()                                 # the one sync of this call
+            for i, code in enumerate(codes[1:]):
+                if code:
+                    who = (f'positive image of item {i}' if i < B else f'negative image of item {i - B}' if i < 2 * B
+                           else f'hard negative of item {hard_items[i - 2 * B]}')
+                    raise ValueError(f'corrupt PNG: {who} (stream {i} of the batch): '
+                                     f'{ops.INFLATE_STATUS.get(code, code)} (inflate status {code})')
+            if codes[0]:
+                raise ValueError(f'corrupt PNG: bad filter byte on scanline {codes[0] - 1}')
+        elif int(status.item()):
             raise ValueError(f'corrupt PNG: bad filter byte on scanline {int(status.item()) - 1}')
         lengths = [len(it['bboxes']) for it in items]
         return [img, neg, torch.cat([it['bboxes'] for it in items], dim=0), torch.cat([it['bird_ids'] for it in items]),

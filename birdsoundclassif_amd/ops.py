@@ -489,6 +489,66 @@ def wav_decode(raw, tag, bits, channels, n, out=None):
     return out[:, :n]
 
 
+INFLATE_STATUS = {1: 'bad zlib header', 2: 'bad block type', 3: 'stored block length check failed',
+                  4: 'bad code lengths in a dynamic header', 5: 'over-subscribed or incomplete code set',
+                  6: 'invalid code', 7: 'distance reaches before the start of the output',
+                  8: 'inflated size differs from the image size', 9: 'payload ends before the stream does',
+                  10: 'Adler-32 mismatch', 11: 'bad payload table row'}       # NBM_INFLATE_* of include/nbm_hip.h
+
+
+def png_payload_pack(streams):
+    """Host only.  list of bytes (one zlib stream each) -> (uint8 array holding them back to back, int64 [n, 2] table of
+    (offset, length)).  Every stream starts on a 16-byte boundary and the array ends at least 8 bytes behind the last
+    stream (zeros), so an 8-byte read at any payload byte stays inside it; its size is a multiple of 16."""
+    import numpy as np
+    table = np.zeros((len(streams), 2), dtype=np.int64)
+    off = 0
+    for i, s in enumerate(streams):
+        table[i] = off, len(s)
+        off += (len(s) + 15) // 16 * 16
+    packed = np.zeros(((off + 8 + 15) // 16 * 16,), dtype=np.uint8)
+    for (o, n), s in zip(table, streams):
+        packed[o:o + n] = np.frombuffer(s, dtype=np.uint8)
+    return packed, table
+
+
+def png_inflate(payload, table, H, W, out=None, status=None):
+    """payload uint8 [bytes] (device: `png_payload_pack`'s array), table int64 [n, 2] (host: numpy or CPU tensor) ->
+    (raw uint8 [n, H * (W + 1)], status int32 [n]), both on the device: the filtered scanlines `zlib.decompress` returns
+    for every stream whose status is 0 (`INFLATE_STATUS` names the others; this call does not read the status back).
+    `raw` is a view of rows whose pitch is a multiple of 16: hand its stride(0) on.  `out`: such rows to write into
+    (uint8 [>= n, pitch >= H * (W + 1)], unit stride along a row); `status`: int32 [n] on the device to write into."""
+    if not (isinstance(payload, torch.Tensor) and payload.is_cuda):
+        raise RuntimeError('payload: the NBM HIP path needs CUDA (ROCm) tensors; no CPU fallback exists')
+    _chk(payload, torch.uint8, 'payload')
+    table = torch.as_tensor(table)
+    if table.is_cuda or table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2:
+        raise ValueError('table: expected int64 [n, 2] (offset, length) rows on the host')
+    n, expect = table.shape[0], int(H) * (int(W) + 1)
+    if payload.dim() != 1 or n < 1 or H < 1 or W < 1 or expect > 1 << 30:
+        raise ValueError(f'payload [{tuple(payload.shape)}], {n} streams, {H} x {W}: shapes that cannot be right')
+    if payload.data_ptr() % 16:
+        raise ValueError('payload: must start on a 16-byte boundary')
+    off, length = table[:, 0], table[:, 1]
+    if bool((off % 16 != 0).any()):
+        raise ValueError('table: every stream must start on a 16-byte boundary of the payload')
+    if bool((off < 0).any()) or bool((length < 0).any()) or bool((off + length > payload.numel()).any()):
+        raise ValueError(f'table: a stream lies outside the payload of {payload.numel()} bytes')
+    if out is None:
+        out = torch.empty((n, (expect + 15) // 16 * 16), dtype=torch.uint8, device=payload.device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] >= n and out.shape[1] >= expect
+              and out.stride(1) == 1 and out.data_ptr() % 16 == 0 and (n == 1 or out.stride(0) % 16 == 0)):
+        raise ValueError('out: expected 16-byte aligned uint8 [>= n, >= H * (W + 1)] rows on the device, pitch a multiple of 16')
+    if status is None:
+        status = torch.empty((n,), dtype=torch.int32, device=payload.device)
+    elif _chk(status, torch.int32, 'status').shape != (n,):
+        raise ValueError(f'status: expected int32 [{n}]')
+    table_dev = table.contiguous().pin_memory().to(payload.device, non_blocking=True)     # pinned: the copy may outlive `table`
+    check(lib().nbm_png_inflate(_ptr(payload), payload.numel(), _ptr(table_dev), n, _ptr(out),
+                                out.stride(0) if n > 1 else out.shape[1], expect, _ptr(status), _stream()), 'nbm_png_inflate')
+    return out[:n, :expect], status
+
+
 def resample_to_wave(x, out_ld, lead, L, M, taps, reflect=False, first=0, count=None, quant16=True):
     """x f32 [batch, n] at any rate -> f32 [batch, out_ld] laid out like `pcm16_to_wave`: the piece [first, first+count)
     of the 44.1 kHz signal = x itself (L = M = 1) or its rational L / M polyphase resampling with the float64 `taps`

@@ -47,6 +47,8 @@ def get_args_parser():
     a('--tf_num_encoder_layers', default=6, type=int); a('--tf_dim_feedforward', default=1024, type=int)
     a('--pyramid_top_n_attn', default=2, type=int); a('--num_classes', default=150, type=int)
     a('--validation_prop', default=0.03, type=float)
+    # not a reference flag: workers ship the PNG files' zlib streams and the GPU inflates them (nbm_png_inflate)
+    a('--device_inflate', action='store_true', default=False)
     return p
 
 
@@ -667,7 +669,8 @@ def main(args):
     model, criterion = build_model(args)
     model.to(device)
     optimizer, lr_scheduler = build_optimizer(model, args)
-    dataset = Img_dataset(args.data_path, transform=True, device=args.device, host_noise=getattr(args, 'host_noise', False))
+    dataset = Img_dataset(args.data_path, transform=True, device=args.device, host_noise=getattr(args, 'host_noise', False),
+                          device_inflate=getattr(args, 'device_inflate', False))
     if resume:
         model, optimizer, lr_scheduler, train_indices, val_indices, epoch, steps, best_val_cls_loss = \
             resume_training(save_dir, model, optimizer, lr_scheduler, args.lr_drop)

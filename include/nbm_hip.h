@@ -907,6 +907,36 @@ struct nbm_augment_params {
  * Replaces the pixel half of `imageio.imread` (image_dataset.py:44,62,77); the zlib inflate stays on the host. */
 int nbm_png_unfilter_gray8(const uint8_t* raw, int64_t raw_bs, int batch, int H, int W, uint8_t* out, int64_t out_bs,
                            int32_t* status, void* stream);
+/* DEFLATE decoder (RFC 1950 / 1951) for the IDAT payloads of `batch` PNG files: the half of `imageio.imread`
+ * (image_dataset.py:44,62,77) that nbm_png_unfilter_gray8's comment says "stays on the host", for callers that ship the
+ * file bytes instead (Img_dataset(device_inflate=True)).  payload: one packed buffer of payload_bytes bytes; table[b] =
+ * {offset, length} (int64 pairs, device memory) of stream b, a whole zlib stream; out[b][0 .. expect) = the inflated
+ * bytes, expect = H * (W + 1), exactly what nbm_png_unfilter_gray8 takes as raw (row pitch out_pitch >= expect BYTES;
+ * nothing behind the expect bytes of a row is written); status[b] = NBM_OK or one of the codes below, written for every
+ * stream.  Stored, fixed and dynamic blocks, any number of them, lengths 3..258, distances 1..32768, overlapping copies;
+ * header (CM = 8, window <= 32 KiB, FCHECK; a preset dictionary is refused) and Adler-32 trailer checked; bytes behind
+ * the trailer are ignored, like zlib.decompress does.  No input can make the kernel read outside [offset, offset +
+ * length) of the payload, write outside out[b][0 .. expect), or run longer than expect + 8 * length steps: a stream that
+ * is malformed sets its own status and the others are decoded.  The rows of a failed stream hold unspecified bytes.
+ * payload and out 16-byte aligned, every offset and (batch > 1) out_pitch a multiple of 16 (NBM_EALIGN; a bad table row:
+ * NBM_INFLATE_ETABLE); expect, length <= 2^30.  One kernel launch on `stream`, one wavefront per stream, no atomics,
+ * no workspace (capturable). */
+#define NBM_INFLATE_EHEADER 1       /* zlib header: CM != 8, window > 32 KiB, FCHECK wrong or FDICT set */
+#define NBM_INFLATE_EBLOCKTYPE 2    /* block type 3 */
+#define NBM_INFLATE_ESTORED 3       /* stored block: LEN != ~NLEN */
+#define NBM_INFLATE_ECODELENGTHS 4  /* dynamic header: HLIT > 286, HDIST > 30, a repeat with nothing to repeat or past the
+                                       announced count, no end-of-block code */
+#define NBM_INFLATE_ECODESET 5      /* over-subscribed or incomplete set of code lengths (zlib's rule: incomplete is allowed
+                                       only for a literal/length or distance set whose single code has length 1, and for
+                                       a distance set without any code) */
+#define NBM_INFLATE_ECODE 6         /* a code no symbol owns, literal/length symbol 286 / 287 or distance symbol 30 / 31 */
+#define NBM_INFLATE_EDISTANCE 7     /* distance reaches before the first output byte */
+#define NBM_INFLATE_EOUTPUT 8       /* the stream inflates to more or fewer than `expect` bytes */
+#define NBM_INFLATE_EINPUT 9        /* the payload ends before the stream does */
+#define NBM_INFLATE_EADLER 10       /* Adler-32 of the output differs from the trailer */
+#define NBM_INFLATE_ETABLE 11       /* table row outside the payload, negative, too long or not 16-byte aligned */
+int nbm_png_inflate(const uint8_t* payload, int64_t payload_bytes, const int64_t* table, int batch, uint8_t* out,
+                    int64_t out_pitch, int64_t expect, int32_t* status, void* stream);
 /* half_std[b] = std(float32(img_b / 255), unbiased) / 2 -- the noise scale of image_dataset.py:66 */
 int nbm_image_half_std_u8(const uint8_t* img, int64_t bs, int batch, int64_t n, float* half_std, void* stream);
 /* out[i] = i-th N(0,1) draw of counter stream `seed` (splitmix64 + Box-Muller) -- device stand-in for torch.randn :66 */
