@@ -399,187 +399,6 @@ __global__ void layernorm_kernel(const float* __restrict__ x, long long rows, in
   }
 }
 
-// Multi-head attention over SHORT sequences (Transformer_RCNN: S = images per batch or RoIs per image, <= 128; head
-// dim <= 64).  One workgroup per (batch entry n, head); K and V of the group live in LDS, each wave owns query rows.
-// Token (s, n) is row s * seq_stride + n * batch_stride of q/k/v/out; keys >= *n_valid (device counter) are masked.
-#define MHA_SMAX 128
-__global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                        const float* __restrict__ v, int q_ld, int k_ld, int v_ld,
-                                                        float* __restrict__ out, int out_ld, int S, int nhead, int hd,
-                                                        long long seq_stride, long long batch_stride,
-                                                        const int* __restrict__ n_valid, float scale) {
-  __shared__ float Ks[MHA_SMAX][65];
-  __shared__ float Vs[MHA_SMAX][64];
-  __shared__ float qs[4][64];
-  __shared__ float ps[4][MHA_SMAX];
-  const int n = blockIdx.x / nhead, h = blockIdx.x - n * nhead;
-  const int nv = n_valid ? min(*n_valid, S) : S;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < nv * hd; i += 256) {
-    const int j = i / hd, d = i - j * hd;
-    const long long row = j * seq_stride + n * batch_stride;
-    Ks[j][d] = k[row * k_ld + h * hd + d];
-    Vs[j][d] = v[row * v_ld + h * hd + d];
-  }
-  __syncthreads();
-  for (int r = wave; r < nv; r += 4) {
-    const long long row = r * seq_stride + n * batch_stride;
-    if (lane < hd) qs[wave][lane] = q[row * q_ld + h * hd + lane] * scale;
-    __builtin_amdgcn_wave_barrier();
-    float sc[MHA_SMAX / 64];
-    float m = -INFINITY;
-#pragma unroll
-    for (int t = 0; t < MHA_SMAX / 64; ++t) {
-      const int j = lane + 64 * t;
-      float a = -INFINITY;
-      if (j < nv) {
-        a = 0.f;
-        for (int d = 0; d < hd; ++d) a += qs[wave][d] * Ks[j][d];
-      }
-      sc[t] = a;
-      m = fmaxf(m, a);
-    }
-    m = nbm_wave_max(m);
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < MHA_SMAX / 64; ++t) {
-      const int j = lane + 64 * t;
-      const float e = j < nv ? expf(sc[t] - m) : 0.f;
-      if (j < nv) ps[wave][j] = e;
-      sum += e;
-    }
-    sum = nbm_wave_sum(sum);
-    __builtin_amdgcn_wave_barrier();
-    if (lane < hd) {
-      float o = 0.f;
-      for (int j = 0; j < nv; ++j) o += ps[wave][j] * Vs[j][lane];
-      out[row * out_ld + h * hd + lane] = o / sum;
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-// Segmented form of mha_small_kernel for the evaluation head with per-image RoI counts (nbm_mha_segments): token (b, r) is
-// row b * R + r.  One workgroup per (image b, head) and R query rows of work in each, whatever the segments look like:
-//   ACROSS_ROIS    the one sequence of image b, rows b * R + j, j < n_roi[b], K and V staged by the whole workgroup;
-//   ACROSS_IMAGES  the sequence of slot r is the images first .. first + cnt - 1 of b's segment (rows (first + j) * R + r) and
-//                  exists iff r < n_roi[first].  The cnt images of a segment share its slots out: image first + i takes the
-//                  slots i, i + cnt, ... -- cnt query rows each.  cnt <= MHA_SHORT: every wave takes slots of its own and
-//                  stages their K and V in its own slice of Ks / Vs (no workgroup barrier; B * R * nhead workgroups of 1 - 4
-//                  tokens otherwise); longer: the workgroup stages one slot at a time, as mha_small_kernel does.
-// The workgroup of (b, head) also writes the zeros of its image's rows that are no valid token, so every row of `out` is
-// written.  A table entry that is not a segment holding b within [0, B) with cnt <= max_count makes b's rows zero.
-// mha_segments_row is mha_small_kernel's arithmetic for one query row, expression by expression: the results are the same bits.
-// (hd stays a run-time value as it is there: with a constant 64 the unrolled dot product is compiled into packed multiplies and
-// separate additions where mha_small_kernel has fused multiply-adds, and the last bit moves.)
-#define MHA_SHORT 8
-__device__ __forceinline__ void mha_segments_row(const float* __restrict__ qrow, float* __restrict__ orow, int hd, int nv,
-                                                 float scale, const float (*Kp)[65], const float (*Vp)[64], float* qsw,
-                                                 float* psw, int lane) {
-  if (lane < hd) qsw[lane] = qrow[lane] * scale;
-  __builtin_amdgcn_wave_barrier();
-  float sc[MHA_SMAX / 64];
-  float m = -INFINITY;
-#pragma unroll
-  for (int t = 0; t < MHA_SMAX / 64; ++t) {
-    const int j = lane + 64 * t;
-    float a = -INFINITY;
-    if (j < nv) {
-      a = 0.f;
-      for (int d = 0; d < hd; ++d) a += qsw[d] * Kp[j][d];
-    }
-    sc[t] = a;
-    m = fmaxf(m, a);
-  }
-  m = nbm_wave_max(m);
-  float sum = 0.f;
-#pragma unroll
-  for (int t = 0; t < MHA_SMAX / 64; ++t) {
-    const int j = lane + 64 * t;
-    const float e = j < nv ? expf(sc[t] - m) : 0.f;
-    if (j < nv) psw[j] = e;
-    sum += e;
-  }
-  sum = nbm_wave_sum(sum);
-  __builtin_amdgcn_wave_barrier();
-  if (lane < hd) {
-    float o = 0.f;
-    for (int j = 0; j < nv; ++j) o += psw[j] * Vp[j][lane];
-    orow[lane] = o / sum;
-  }
-  __builtin_amdgcn_wave_barrier();
-}
-
-__global__ __launch_bounds__(256) void mha_segments_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                           const float* __restrict__ v, int q_ld, int k_ld, int v_ld,
-                                                           float* __restrict__ out, int out_ld, int B, int R, int nhead,
-                                                           int hd, int mode, const int* __restrict__ segments,
-                                                           const int* __restrict__ n_roi, int max_count, float scale) {
-  __shared__ float Ks[MHA_SMAX][65];
-  __shared__ float Vs[MHA_SMAX][64];
-  __shared__ float qs[4][64];
-  __shared__ float ps[4][MHA_SMAX];
-  const int b = blockIdx.x / nhead, h = blockIdx.x - b * nhead;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long col = (long long)h * hd;
-  int first = b, cnt = 1;
-  bool ok = true;
-  if (mode == NBM_MHA_ACROSS_IMAGES) {
-    first = segments[b];
-    cnt = segments[B + b];
-    ok = first >= 0 && first <= b && cnt >= 1 && cnt <= max_count && b - first < cnt && first + cnt <= B;
-  }
-  const int n = ok ? min(max(n_roi[first], 0), R) : 0;
-  for (int r = n + wave; r < R; r += 4)
-    if (lane < hd) out[((long long)b * R + r) * out_ld + col + lane] = 0.f;
-  if (mode == NBM_MHA_ACROSS_ROIS) {
-    const long long row0 = (long long)b * R;
-    for (int i = threadIdx.x; i < n * hd; i += 256) {
-      const int j = i / hd, d = i - j * hd;
-      Ks[j][d] = k[(row0 + j) * k_ld + col + d];
-      Vs[j][d] = v[(row0 + j) * v_ld + col + d];
-    }
-    __syncthreads();
-    for (int r = wave; r < n; r += 4)
-      mha_segments_row(q + (row0 + r) * q_ld + col, out + (row0 + r) * out_ld + col, hd, n, scale, Ks, Vs, qs[wave],
-                           ps[wave], lane);
-    return;
-  }
-  const int me = b - first;
-  if (cnt <= MHA_SHORT) {
-    float(*Kw)[65] = Ks + wave * MHA_SHORT;
-    float(*Vw)[64] = Vs + wave * MHA_SHORT;
-    for (int r = me + wave * cnt; r < n; r += 4 * cnt) {
-      if (lane < hd)
-        for (int j = 0; j < cnt; ++j) {
-          const long long row = (long long)(first + j) * R + r;
-          Kw[j][lane] = k[row * k_ld + col + lane];
-          Vw[j][lane] = v[row * v_ld + col + lane];
-        }
-      __builtin_amdgcn_wave_barrier();
-      for (int i = 0; i < cnt; ++i) {
-        const long long row = (long long)(first + i) * R + r;
-        mha_segments_row(q + row * q_ld + col, out + row * out_ld + col, hd, cnt, scale, Kw, Vw, qs[wave], ps[wave], lane);
-      }
-    }
-    return;
-  }
-  for (int r = me; r < n; r += cnt) {                       // r, n, cnt are uniform over the workgroup: so are the barriers
-    __syncthreads();
-    for (int i = threadIdx.x; i < cnt * hd; i += 256) {
-      const int j = i / hd, d = i - j * hd;
-      const long long row = (long long)(first + j) * R + r;
-      Ks[j][d] = k[row * k_ld + col + d];
-      Vs[j][d] = v[row * v_ld + col + d];
-    }
-    __syncthreads();
-    for (int i = wave; i < cnt; i += 4) {
-      const long long row = (long long)(first + i) * R + r;
-      mha_segments_row(q + row * q_ld + col, out + row * out_ld + col, hd, cnt, scale, Ks, Vs, qs[wave], ps[wave], lane);
-    }
-  }
-}
-
 __global__ void silu_kernel(const float* __restrict__ x, float* __restrict__ y, long long n) {
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
        i += (long long)gridDim.x * blockDim.x) {
@@ -814,33 +633,6 @@ extern "C" int nbm_layernorm(const float* x, int64_t rows, int E, const float* w
   if (!x || !w || !b || !y || rows <= 0 || E <= 0) return NBM_EINVAL;
   hipLaunchKernelGGL(layernorm_kernel, dim3(grid_for(rows, 4, 256 * 32)), dim3(256), 0, (hipStream_t)stream, x,
                      (long long)rows, E, w, b, eps, y);
-  return nbm_launch_status();
-}
-
-extern "C" int nbm_mha_small(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out,
-                             int out_ld, int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride,
-                             const int32_t* n_valid, float scale, void* stream) {
-  if (!q || !k || !v || !out || S <= 0 || S > MHA_SMAX || N <= 0 || nhead <= 0 || hd <= 0 || hd > 64) return NBM_EINVAL;
-  if (q_ld < nhead * hd || k_ld < nhead * hd || v_ld < nhead * hd || out_ld < nhead * hd) return NBM_EINVAL;
-  hipLaunchKernelGGL(mha_small_kernel, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out,
-                     out_ld, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid, scale);
-  return nbm_launch_status();
-}
-
-extern "C" int nbm_mha_segments(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out,
-                                int out_ld, int B, int R, int nhead, int hd, int mode, const int32_t* segments,
-                                const int32_t* n_roi, int max_count, float scale, void* stream) {
-  if (!q || !k || !v || !out || !n_roi || B <= 0 || R <= 0 || nhead <= 0 || hd <= 0 || hd > 64) return NBM_EINVAL;
-  if (q_ld < nhead * hd || k_ld < nhead * hd || v_ld < nhead * hd || out_ld < nhead * hd) return NBM_EINVAL;
-  if (mode == NBM_MHA_ACROSS_ROIS) {
-    if (R > MHA_SMAX) return NBM_EINVAL;
-  } else if (mode == NBM_MHA_ACROSS_IMAGES) {
-    if (!segments || max_count < 1 || max_count > MHA_SMAX) return NBM_EINVAL;
-  } else {
-    return NBM_EINVAL;
-  }
-  hipLaunchKernelGGL(mha_segments_kernel, dim3(B * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out,
-                     out_ld, B, R, nhead, hd, mode, segments, n_roi, max_count, scale);
   return nbm_launch_status();
 }
 

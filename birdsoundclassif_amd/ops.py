@@ -858,7 +858,7 @@ def mha_small(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid=None):
     return out
 
 
-MHA_SMAX = 128                  # csrc/pointwise.hip: longest sequence of nbm_mha_small / nbm_mha_segments
+MHA_SMAX = 128                  # csrc/mha.hip: longest sequence of nbm_mha_small / nbm_mha_segments
 MHA_ACROSS_ROIS, MHA_ACROSS_IMAGES = 0, 1
 
 

@@ -781,7 +781,7 @@ int nbm_mha_small_bwd(const float* q, const float* k, const float* v, const floa
                       int go_ld, float* gq, float* gk, float* gv, int gq_ld, int gk_ld, int gv_ld, float* workspace, int S,
                       int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                       float scale, void* stream);
-/* ---- dropout of the Transformer_RCNN head in training mode, `--tf_rcnn --dropout p` (csrc/dropout.hip).  A mask is a pure function
+/* ---- dropout of the Transformer_RCNN head in training mode, `--tf_rcnn --dropout p` (csrc/dropout.hip, csrc/mha.hip).  A mask is a pure function
  * of (seed, call, site_id, element index) -- Philox4x32-10, csrc/nbm_philox.h: counter (q & 0xffffffff, q >> 32, site_id, call) with
  * q = element index >> 2, key = (low, high) half of `seed`, element i takes output word i & 3 and is kept iff word >= threshold
  * (threshold = round(p * 2^32)); a kept element is multiplied by `scale` = float32(1) / float32(1 - p), computed by the caller.

@@ -1,4 +1,4 @@
-"""Training forward + backward of the transformer head (`--tf_rcnn`) with and without dropout (csrc/dropout.hip); writes
+"""Training forward + backward of the transformer head (`--tf_rcnn`) with and without dropout (csrc/dropout.hip, csrc/mha.hip); writes
 profiles/tf_dropout.txt and prints one JSON line.
 
     python scripts/bench_tf_dropout.py [--batch 128] [--rois 16] [--layers 6] [--ps 0,0.1] [--rounds 7] [--window_ms 200]
@@ -85,8 +85,8 @@ def main():
                     'three backward, its two residual additions leave the GEMM epilogues for them, and the attention kernels evaluate '
                     'Philox4x32-10 once per probability.\n')
             if parent is not None:
-                f.write('\nParent commit, p = 0, same command in a process of its own in the same session (the p = 0 launches are '
-                        'identical, so the figures should agree within the spread shown):\n')
+                f.write('\nParent commit, same command in a process of its own in the same session (where its launches are the same the '
+                        'figures should agree within the spread shown):\n')
                 for r in parent['rows']:
                     f.write(f'{r["flavour"]:10s} {r["p"]:5.2f} {r["median_us"]:10.1f} {r["min_us"]:10.1f} {r["max_us"]:10.1f} '
                             f'{r["steps_per_window"]:13d}\n')

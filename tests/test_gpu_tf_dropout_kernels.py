@@ -1,4 +1,4 @@
-"""GPU: the dropout kernels of the transformer head (csrc/dropout.hip) against their specification -- `nbm_dropout` bit for bit
+"""GPU: the dropout kernels of the transformer head (csrc/dropout.hip, csrc/mha.hip) against their specification -- `nbm_dropout` bit for bit
 against NumPy float32 with the mask of `ops.dropout_keep_reference`, `nbm_mha_small_drop` and its backward against float64 torch
 attention with that mask injected on the probabilities.  Deterministic: no statistics, no use of torch's generator."""
 import ctypes as C
@@ -112,8 +112,10 @@ def close(got, ref, tol, name):
     assert err <= tol * scale, f'{name}: max err {err:.3e} vs scale {scale:.3e}'
 
 
-def attention_f64(qkv, go, seq_major, S, N, n_use, keep, scale):
+def attention_f64(qkv, go, seq_major, S, N, n_use, keep, scale, NH=NH):
     """float64 attention with the keep mask [N, NH, S, S] on the probabilities -> (out [n_use, N, E], d/dqkv [S*N, 3E])."""
+    E = go.shape[1]
+    HD = E // NH
     qkv = qkv.double().requires_grad_(True)
     t = qkv.view(S, N, 3 * E) if seq_major else qkv.view(N, S, 3 * E).transpose(0, 1)
     q, k, v = (t[..., i * E:(i + 1) * E].reshape(S, N * NH, HD).transpose(0, 1) for i in range(3))
@@ -157,6 +159,65 @@ def test_mha_small_drop_forward_and_backward(seq_major, S, N, nv, p):
     g2 = ops.mha_small_drop_bwd(qd.detach()[:, :E], qd.detach()[:, E:2 * E], qd.detach()[:, 2 * E:], (go * valid).cuda(), S, N, NH,
                                 ss, bs, cnt, p, SEED, call, site)
     assert torch.equal(torch.cat(g2, 1), qd.grad)
+
+
+# hd = 24: lanes 24 .. 63 of a wave own no output column and a staged K / V row is 24 floats; S = 66 crosses the 64 lanes of a score row
+GEOMS_HD24 = [(False, 5, 2, 3), (True, 66, 1, None)]
+
+
+@pytest.mark.parametrize('seq_major,S,N,nv', GEOMS_HD24)
+def test_mha_small_and_drop_with_a_head_dimension_below_64(seq_major, S, N, nv):
+    """E = 96, 4 heads.  Bounds of the hd = 64 tests: 3e-6 forward, 3e-5 gradients, relative to the largest reference value (sums
+    of 24 instead of 64 products cannot need more)."""
+    E, NH, p, call, site = 96, 4, 0.5, 6, 2
+    qkv = torch.from_numpy(rnd(('mha24', seq_major, S), S * N, 3 * E))
+    go = torch.from_numpy(rnd(('mha24g', seq_major, S), S * N, E))
+    n_use = S if nv is None else nv
+    cnt = None if nv is None else torch.tensor([nv], dtype=torch.int32, device='cuda')
+    ss, bs = (N, 1) if seq_major else (1, S)
+    valid = torch.zeros(S, N, 1)
+    valid[:n_use] = 1
+    valid = (valid if seq_major else valid.transpose(0, 1)).reshape(S * N, 1)
+    every = torch.ones(N, NH, S, S, dtype=torch.bool)
+    dropped = torch.from_numpy(ops.dropout_keep_reference(SEED, call, site, N * NH * S * S, p)).view(N, NH, S, S)
+    for name, keep, scale in (('mha hd24', every, 1.0), ('mha drop hd24', dropped, ops.dropout_params(p)[1])):
+        ref, gref = attention_f64(qkv, go, seq_major, S, N, n_use, keep, scale, NH)
+        qd = qkv.cuda().requires_grad_(True)
+        q, k, v = qd[:, :E], qd[:, E:2 * E], qd[:, 2 * E:]
+        if keep is every:
+            out = Fn.MhaSmall.apply(q, k, v, S, N, NH, ss, bs, cnt)
+        else:
+            out = Fn.MhaSmallDrop.apply(q, k, v, S, N, NH, ss, bs, cnt, p, SEED, call, site)
+        got = out.view(S, N, E) if seq_major else out.view(N, S, E).transpose(0, 1)
+        close(got[:n_use], ref, 3e-6, name + ' fwd')
+        out.backward((go * valid).cuda())
+        close(qd.grad, gref, 3e-5, name + ' dqkv')
+        if (valid == 0).any():
+            assert float(qd.grad.cpu()[valid[:, 0] == 0].abs().max()) == 0.0
+            assert float(out.detach().cpu()[valid[:, 0] == 0].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize('mode', [ops.MHA_ACROSS_ROIS, ops.MHA_ACROSS_IMAGES])
+def test_mha_segments_is_mha_small_with_a_head_dimension_below_64(mode):
+    """Two segments of 2 and 1 images, 5 RoI slots, 3 and 5 of them filled: every valid row holds the bits `ops.mha_small` gives on
+    its segment alone, every other row is zero."""
+    E, NH, R, sizes, counts = 96, 4, 5, [2, 1], [3, 5]
+    qkv = torch.from_numpy(rnd(('mha24seg', mode), sum(sizes) * R, 3 * E)).cuda()
+    n_roi = torch.tensor(np.repeat(counts, sizes), dtype=torch.int32, device='cuda')
+    out = ops.mha_segments(qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:], R, NH, mode, ops.segment_table(sizes), n_roi)
+    s = 0
+    for m, n in zip(sizes, counts):
+        part = qkv[s * R:(s + m) * R]
+        q, k, v = part[:, :E], part[:, E:2 * E], part[:, 2 * E:]
+        if mode == ops.MHA_ACROSS_ROIS:                            # m sequences of the image's n RoIs
+            ref = ops.mha_small(q, k, v, R, m, NH, 1, R, torch.tensor([n], dtype=torch.int32, device='cuda'))
+        else:                                                      # R sequences of the segment's m images, n of them real
+            ref = ops.mha_small(q, k, v, m, R, NH, R, 1)
+        ok = (torch.arange(m * R, device='cuda') % R) < n
+        assert torch.equal(out[s * R:(s + m) * R][ok], ref[ok]), (s, m, n)
+        assert not out[s * R:(s + m) * R][~ok].any()
+        s += m
+    assert torch.isfinite(out).all()
 
 
 @pytest.mark.parametrize('seq_major,S,N,nv', [GEOMS[2], GEOMS[4]])
