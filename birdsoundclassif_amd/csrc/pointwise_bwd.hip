@@ -331,36 +331,25 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ gy, int B, int Hi,
     const int X = xc / C4, c = xc - X * C4;
     const int Y = blockIdx.y, b = blockIdx.z;
     const long long i = ((long long)(b * Hi + Y) * Wi + X) * C4 + c;
-    // The fine rows / columns whose interpolation touches coarse row Y / column X, with their weights: found ONCE per axis (up to
-    // MAXT of them: ~2 / scale + 1), then a dense double loop over the two short lists -- the original form re-derived the column
-    // weights for every candidate row and walked ~5 x 5 candidates of which <= 3 x 3 contribute.  (Measured at 188x512 -> 94x256 x 384,
-    // B = 64: 4.36 ms flat 64-bit index + candidate walk -> 4.7 ms with the lists alone (!) -> 3.57 ms with 32-bit indices; skipping the
-    // 61 % of the fine pixels that are known zeros in the data gradient of the demand-driven level -- pattern test + tile bitmap -- made
-    // it SLOWER, 4.26 ms: the reads are L2 hits, the tests are not free.  Not kept.  Two more forms measured at B = 128 (6.86 ms, 18.9 GB
-    // read = 2.8 TB/s) and not kept either: one contiguous band of coarse rows per XCD (6.82 ms) and the per-axis lists derived once per
-    // workgroup and shared through LDS instead of once per thread (7.03 ms) -- it is neither L2 locality nor the list arithmetic.)
+    // The fine columns whose interpolation touches coarse column X are collected, with their weights, into a list of MAXT entries
+    // (~2 / scale + 1 of them exist), and the candidate rows are walked against that list, each row's weight derived once per row.
+    // A scale with more contributors than MAXT (up-sampling by more than ~2.5x; sw == 0: every fine column) refills the list and
+    // walks the rows again, chunk after chunk of columns: no contributor is dropped at any scale.  With one chunk the sum runs row
+    // by row, column by column, the order the double list of earlier versions had.  (Measured at 188x512 -> 94x256 x 384, B = 64:
+    // 4.36 ms flat 64-bit index + candidate walk -> 3.57 ms with per-axis lists and 32-bit indices; skipping the 61 % of the fine
+    // pixels that are known zeros in the data gradient of the demand-driven level -- pattern test + tile bitmap -- made it SLOWER,
+    // 4.26 ms: the reads are L2 hits, the tests are not free.  Not kept.  Neither were one contiguous band of coarse rows per XCD
+    // nor lists derived once per workgroup and shared through LDS: it is neither L2 locality nor the list arithmetic.)
     constexpr int MAXT = 6;
-    int ys[MAXT], xs[MAXT], ny = 0, nx = 0;
-    float wys[MAXT], wxs[MAXT];
-    {
-      int lo = sh > 0.f ? (int)floorf((Y - 1) / sh) - 1 : 0, hi = sh > 0.f ? (int)ceilf((Y + 1) / sh) + 1 : Ho - 1;
-      lo = max(lo, 0); hi = min(hi, Ho - 1);
-      for (int oy = lo; oy <= hi; ++oy) {
-        if (pat && ((oy + 2) % pat >= 5 || (oy + 2) / pat > (Ho - 1) / pat)) continue;
-        const float fy = sh * oy;
-        const int y0 = (int)fy, y1 = y0 + (y0 < Hi - 1 ? 1 : 0);
-        const float ly = fminf(fmaxf(fy - y0, 0.f), 1.f);
-        float wy = 0.f;
-        if (y0 == Y) wy += 1.f - ly;
-        if (y1 == Y) wy += ly;
-        if (wy == 0.f) continue;
-#pragma unroll
-        for (int k = 0; k < MAXT; ++k) if (k == ny) { ys[k] = oy; wys[k] = wy; }
-        if (ny < MAXT) ++ny;
-      }
-      lo = sw > 0.f ? (int)floorf((X - 1) / sw) - 1 : 0; hi = sw > 0.f ? (int)ceilf((X + 1) / sw) + 1 : Wo - 1;
-      lo = max(lo, 0); hi = min(hi, Wo - 1);
-      for (int ox = lo; ox <= hi; ++ox) {
+    int ylo = sh > 0.f ? (int)floorf((Y - 1) / sh) - 1 : 0, yhi = sh > 0.f ? (int)ceilf((Y + 1) / sh) + 1 : Ho - 1;
+    ylo = max(ylo, 0); yhi = min(yhi, Ho - 1);
+    int xlo = sw > 0.f ? (int)floorf((X - 1) / sw) - 1 : 0, xhi = sw > 0.f ? (int)ceilf((X + 1) / sw) + 1 : Wo - 1;
+    xlo = max(xlo, 0); xhi = min(xhi, Wo - 1);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int ox = xlo; ox <= xhi;) {
+      int xs[MAXT], nx = 0;
+      float wxs[MAXT];
+      for (; ox <= xhi && nx < MAXT; ++ox) {
         if (pat && ((ox + 2) % pat >= 5 || (ox + 2) / pat > (Wo - 1) / pat)) continue;
         const float fx = sw * ox;
         const int x0 = (int)fx, x1 = x0 + (x0 < Wi - 1 ? 1 : 0);
@@ -371,22 +360,25 @@ __global__ void upsample_bwd_kernel(const float* __restrict__ gy, int B, int Hi,
         if (wx == 0.f) continue;
 #pragma unroll
         for (int k = 0; k < MAXT; ++k) if (k == nx) { xs[k] = ox; wxs[k] = wx; }
-        if (nx < MAXT) ++nx;
+        ++nx;
       }
-    }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+      if (nx == 0) break;                                                // the candidate range is exhausted
+      for (int oy = ylo; oy <= yhi; ++oy) {
+        if (pat && ((oy + 2) % pat >= 5 || (oy + 2) / pat > (Ho - 1) / pat)) continue;
+        const float fy = sh * oy;
+        const int y0 = (int)fy, y1 = y0 + (y0 < Hi - 1 ? 1 : 0);
+        const float ly = fminf(fmaxf(fy - y0, 0.f), 1.f);
+        float wy = 0.f;
+        if (y0 == Y) wy += 1.f - ly;
+        if (y1 == Y) wy += ly;
+        if (wy == 0.f) continue;
 #pragma unroll
-    for (int a = 0; a < MAXT; ++a) {
-      if (a >= ny) break;
-      const int oy = ys[a];
-      const float wy = wys[a];
-#pragma unroll
-      for (int e = 0; e < MAXT; ++e) {
-        if (e >= nx) break;
-        const int ox = xs[e];
-        const f32x4 g = g4[((long long)(b * Ho + oy) * Wo + ox) * C4 + c];
-        const float w = wy * wxs[e];
-        acc[0] += w * g[0]; acc[1] += w * g[1]; acc[2] += w * g[2]; acc[3] += w * g[3];
+        for (int e = 0; e < MAXT; ++e) {
+          if (e >= nx) break;
+          const f32x4 g = g4[((long long)(b * Ho + oy) * Wo + xs[e]) * C4 + c];
+          const float w = wy * wxs[e];
+          acc[0] += w * g[0]; acc[1] += w * g[1]; acc[2] += w * g[2]; acc[3] += w * g[3];
+        }
       }
     }
     o4[i] = acc;
