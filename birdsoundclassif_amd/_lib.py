@@ -129,6 +129,7 @@ SIGNATURES = {
     'nbm_layernorm': [_P, _L, _I, _P, _P, _F, _P, _P],
     'nbm_mha_small': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _L, _L, _P, _F, _P],
     'nbm_mha_segments': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P],
+    'nbm_mha_segments_wide': [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _F, _P],
     'nbm_pair_softmax': [_P, _L, _I, _I, _P, _I, _P],
     'nbm_rpn_decode': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     'nbm_nan_images': [_P, _I, _L, _P, _P],

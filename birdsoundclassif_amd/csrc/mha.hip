@@ -1,7 +1,9 @@
 // Multi-head attention of the Transformer_RCNN head (`--tf_rcnn`) over SHORT sequences: S = images per batch or RoIs per image,
-// <= MHA_SMAX; head dim <= MHA_HDMAX.  Every attention kernel of the head is here -- evaluation (nbm_mha_small), segmented bulk
-// evaluation (nbm_mha_segments), training with and without dropout on the softmax probabilities (nbm_mha_small_drop, the two
-// backwards) -- and every one of them gets a query row's arithmetic from one place: mha_row forward, mha_bwd_rows_kernel backward.
+// <= MHA_SMAX; head dim <= MHA_HDWIDE (one lane per output column up to MHA_HDMAX, the chunked wide kernels above it; the host
+// launchers choose).  Every attention kernel of the head is here -- evaluation (nbm_mha_small), segmented bulk
+// evaluation (nbm_mha_segments, which keeps its limit of MHA_HDMAX, and nbm_mha_segments_wide), training with and without
+// dropout on the softmax probabilities (nbm_mha_small_drop, the two backwards) -- and every one of them gets a query row's arithmetic from one place: mha_row forward, mha_bwd_rows_kernel backward
+// (mha_wide_rows and mha_wide_bwd_rows_kernel for the wide heads).
 // Dropout masks come from the counter generator of nbm_philox.h and are never stored: the backward evaluates them again.
 #include <initializer_list>
 #include "nbm_common.h"
@@ -9,7 +11,11 @@
 
 #define MHA_SMAX 128      // longest sequence: a score row is MHA_SMAX / 64 values per lane (ops.MHA_SMAX mirrors it)
 #define MHA_SHORT 8       // nbm_mha_segments: segments of up to this many images are a wave's own work
-#define MHA_HDMAX 64      // head dim: one lane per output column
+#define MHA_HDMAX 64      // head dim of the narrow kernels: one lane per output column
+#define MHA_HDWIDE 512    // head dim of the wide kernels: 64-column chunks of K and V pass through LDS
+#define MHA_WROWS 8       // wide kernels: query rows a wave carries through the chunks ...
+#define MHA_WBLOCK 32     // ... and a workgroup
+#define MHA_KEYBLOCKS 4   // wide backward, pass 2: sets of key rows per (entry, head, chunk)
 
 namespace {
 
@@ -297,9 +303,297 @@ __global__ __launch_bounds__(256) void mha_bwd_keys_kernel(
   }
 }
 
+// --------------------------------------------------------------------------------- wide heads: MHA_HDMAX < hd <= MHA_HDWIDE
+// K and V of one (entry, head) no longer fit LDS whole (2 x 128 x 512 x 4 bytes at the limit), so the head dimension is staged
+// in chunks of 64 columns and the probabilities of a block of query rows wait in LDS between the two products.  A wave carries
+// MHA_WROWS query rows through every chunk -- one LDS read of K[j][d] or V[j][c] serves all of them -- and a workgroup a block of
+// MHA_WBLOCK.  As on the narrow path every entry point gets a query row's arithmetic from one place (mha_wide_dots, the softmax
+// of mha_wide_rows, mha_wide_pv; the backward's softmax in mha_wide_bwd_rows_kernel), and every product-sum is an explicit fmaf
+// chain in ascending d or j: the bits of a row depend neither on the chunking nor on which wave, block or kernel computed it.
+static_assert(MHA_SHORT <= MHA_WROWS && MHA_WBLOCK == 4 * MHA_WROWS && MHA_SMAX % 64 == 0, "wide attention: a wave's rows");
+
+struct MhaWideLds {
+  float Y[MHA_SMAX][65];                  // the current 64-column chunk of K or V, one row per key
+  float x[MHA_WBLOCK][64];                // the same chunk of the query-side rows (q * scale, or dO); wave w owns rows 8w .. 8w + 7
+  float P[MHA_WBLOCK][MHA_SMAX];          // forward: the probabilities of those rows; backward: dS
+};
+
+// A sequence: key / query j is row off + j * stride of every operand, nv of them.
+struct MhaSeq {
+  long long off, stride;
+  int nv;
+};
+
+// WG = true: the workgroup stages Y (all of it) and shares it; false: the wave stages its own sequence of <= MHA_SHORT keys in
+// its MHA_WROWS-row slice of Y and meets no workgroup barrier.
+template <bool WG>
+__device__ __forceinline__ void mha_wide_sync() {
+  if constexpr (WG) __syncthreads();
+  else __builtin_amdgcn_wave_barrier();
+}
+
+template <bool WG>
+__device__ __forceinline__ void mha_wide_stage(float (*Y)[65], const float* __restrict__ src, int ld, long long col, int dn,
+                                               const MhaSeq& sq) {
+  for (int i = WG ? threadIdx.x : (threadIdx.x & 63); i < sq.nv * 64; i += WG ? 256 : 64) {
+    const int j = i >> 6, d = i & 63;
+    if (d < dn) Y[j][d] = src[(sq.off + j * sq.stride) * ld + col + d];
+  }
+}
+
+// acc[i][t] += sum_d (xsrc[query rw0 + i][d] * xmul) * ysrc[key lane + 64 t][d] over the whole head dimension.
+template <bool WG>
+__device__ __forceinline__ void mha_wide_dots(float (&acc)[MHA_WROWS][MHA_SMAX / 64], const float* __restrict__ xsrc, int x_ld,
+                                              float xmul, const float* __restrict__ ysrc, int y_ld, long long col, int hd,
+                                              const MhaSeq& sq, int rw0, MhaWideLds& L, float (*Y)[65]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float(*xw)[64] = L.x + wave * MHA_WROWS;
+  for (int c0 = 0; c0 < hd; c0 += 64) {
+    const int dn = min(64, hd - c0);
+    mha_wide_sync<WG>();                                    // the last readers of Y and x are done
+    mha_wide_stage<WG>(Y, ysrc, y_ld, col + c0, dn, sq);
+#pragma unroll
+    for (int i = 0; i < MHA_WROWS; ++i) {
+      const int r = rw0 + i;
+      xw[i][lane] = (r < sq.nv && lane < dn) ? xsrc[(sq.off + r * sq.stride) * x_ld + col + c0 + lane] * xmul : 0.f;
+    }
+    mha_wide_sync<WG>();
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) {
+      const int j = lane + 64 * t;
+      if (j < sq.nv)
+        for (int d = 0; d < dn; ++d) {
+          const float y = Y[j][d];
+#pragma unroll
+          for (int i = 0; i < MHA_WROWS; ++i) acc[i][t] = fmaf(xw[i][d], y, acc[i][t]);
+        }
+    }
+  }
+}
+
+// put(i, c, sum_j P[query rw0 + i][j] * ysrc[key j][c]) for the wave's rows i and every column c < hd.
+template <bool WG, class Put>
+__device__ __forceinline__ void mha_wide_pv(const float* __restrict__ ysrc, int y_ld, long long col, int hd, const MhaSeq& sq,
+                                            MhaWideLds& L, float (*Y)[65], Put&& put) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float(*Pw)[MHA_SMAX] = L.P + wave * MHA_WROWS;
+  for (int c0 = 0; c0 < hd; c0 += 64) {
+    const int dn = min(64, hd - c0);
+    mha_wide_sync<WG>();
+    mha_wide_stage<WG>(Y, ysrc, y_ld, col + c0, dn, sq);
+    mha_wide_sync<WG>();
+    if (lane < dn) {
+      float o[MHA_WROWS] = {};
+      for (int j = 0; j < sq.nv; ++j) {
+        const float y = Y[j][lane];
+#pragma unroll
+        for (int i = 0; i < MHA_WROWS; ++i) o[i] = fmaf(Pw[i][j], y, o[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < MHA_WROWS; ++i) put(i, c0 + lane, o[i]);
+    }
+  }
+}
+
+// The queries rw0 .. rw0 + MHA_WROWS - 1 of sequence sq by one wave, in the two forms of mha_row.  mask_base: the first mask
+// element of the sequence's (entry, head); mask_S: the mask tensor's S.
+template <bool DROP, bool WG>
+__device__ __forceinline__ void mha_wide_rows(const float* __restrict__ q, const float* __restrict__ k,
+                                              const float* __restrict__ v, int q_ld, int k_ld, int v_ld, float* __restrict__ out,
+                                              int out_ld, long long col, int hd, const MhaSeq& sq, int rw0, float scale,
+                                              const MhaDrop& dr, uint64_t mask_base, int mask_S, MhaWideLds& L, float (*Y)[65]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float(*Pw)[MHA_SMAX] = L.P + wave * MHA_WROWS;
+  float acc[MHA_WROWS][MHA_SMAX / 64] = {};
+  mha_wide_dots<WG>(acc, q, q_ld, scale, k, k_ld, col, hd, sq, rw0, L, Y);
+  float sum[MHA_WROWS];
+#pragma unroll
+  for (int i = 0; i < MHA_WROWS; ++i) {
+    const int r = rw0 + i;
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) m = fmaxf(m, lane + 64 * t < sq.nv ? acc[i][t] : -INFINITY);
+    m = nbm_wave_max(m);
+    float s = 0.f;
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) {
+      acc[i][t] = lane + 64 * t < sq.nv ? expf(acc[i][t] - m) : 0.f;
+      s += acc[i][t];
+    }
+    s = nbm_wave_sum(s);
+    sum[i] = s;
+    const uint64_t row_base = mask_base + (uint64_t)r * (uint64_t)mask_S;
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) {
+      const int j = lane + 64 * t;
+      if (j < sq.nv && r < sq.nv) {
+        if constexpr (DROP) Pw[i][j] = mha_keep(dr, row_base, j) ? (acc[i][t] / s) * dr.drop_scale : 0.f;
+        else Pw[i][j] = acc[i][t];
+      }
+    }
+  }
+  mha_wide_pv<WG>(v, v_ld, col, hd, sq, L, Y, [&](int i, int c, float o) {
+    const int r = rw0 + i;
+    if (r < sq.nv) out[(sq.off + r * sq.stride) * out_ld + col + c] = DROP ? o : o / sum[i];
+  });
+}
+
+// nbm_mha_small / nbm_mha_small_drop, wide: one workgroup per (batch entry n, head) and block of MHA_WBLOCK query rows.
+template <bool DROP>
+__global__ __launch_bounds__(256) void mha_wide_small_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                             const float* __restrict__ v, int q_ld, int k_ld, int v_ld,
+                                                             float* __restrict__ out, int out_ld, int S, int nhead, int hd,
+                                                             long long seq_stride, long long batch_stride,
+                                                             const int* __restrict__ n_valid, float scale, MhaDrop dr) {
+  __shared__ MhaWideLds L;
+  const int n = blockIdx.x / nhead, h = blockIdx.x - n * nhead;
+  const int nv = n_valid ? min(*n_valid, S) : S;
+  const int r0 = blockIdx.y * MHA_WBLOCK;
+  if (r0 >= nv) return;
+  const MhaSeq sq = {n * batch_stride, seq_stride, nv};
+  mha_wide_rows<DROP, true>(q, k, v, q_ld, k_ld, v_ld, out, out_ld, (long long)h * hd, hd, sq,
+                            r0 + (int)(threadIdx.x >> 6) * MHA_WROWS, scale, dr, (uint64_t)blockIdx.x * (uint64_t)S * (uint64_t)S,
+                            S, L, L.Y);
+}
+
+// nbm_mha_segments, wide: mha_segments_kernel's division of the work -- a workgroup per (image b, head), in ACROSS_ROIS times a
+// block of query rows -- with the rows going through mha_wide_rows<false>, as the wide nbm_mha_small's do.
+__global__ __launch_bounds__(256) void mha_wide_segments_kernel(const float* __restrict__ q, const float* __restrict__ k,
+                                                                const float* __restrict__ v, int q_ld, int k_ld, int v_ld,
+                                                                float* __restrict__ out, int out_ld, int B, int R, int nhead,
+                                                                int hd, int mode, const int* __restrict__ segments,
+                                                                const int* __restrict__ n_roi, int max_count, float scale) {
+  __shared__ MhaWideLds L;
+  const int b = blockIdx.x / nhead, h = blockIdx.x - b * nhead;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long col = (long long)h * hd;
+  const MhaDrop none = {};
+  int first = b, cnt = 1;
+  bool ok = true;
+  if (mode == NBM_MHA_ACROSS_IMAGES) {
+    first = segments[b];
+    cnt = segments[B + b];
+    ok = first >= 0 && first <= b && cnt >= 1 && cnt <= max_count && b - first < cnt && first + cnt <= B;
+  }
+  const int n = ok ? min(max(n_roi[first], 0), R) : 0;
+  for (int r = n + wave + 4 * (int)blockIdx.y; r < R; r += 4 * (int)gridDim.y)
+    for (int c = lane; c < hd; c += 64) out[((long long)b * R + r) * out_ld + col + c] = 0.f;
+  if (mode == NBM_MHA_ACROSS_ROIS) {
+    const MhaSeq sq = {(long long)b * R, 1, n};
+    for (int r0 = blockIdx.y * MHA_WBLOCK; r0 < n; r0 += gridDim.y * MHA_WBLOCK)
+      mha_wide_rows<false, true>(q, k, v, q_ld, k_ld, v_ld, out, out_ld, col, hd, sq, r0 + wave * MHA_WROWS, scale, none, 0, 0, L,
+                                 L.Y);
+    return;
+  }
+  const int me = b - first;
+  if (cnt <= MHA_SHORT) {                                   // a slot's cnt queries are one wave's rows
+    for (int r = me + wave * cnt; r < n; r += 4 * cnt) {
+      const MhaSeq sq = {(long long)first * R + r, R, cnt};
+      mha_wide_rows<false, false>(q, k, v, q_ld, k_ld, v_ld, out, out_ld, col, hd, sq, 0, scale, none, 0, 0, L,
+                                  L.Y + wave * MHA_WROWS);
+    }
+    return;
+  }
+  for (int r = me; r < n; r += cnt) {                       // r, n, cnt are uniform over the workgroup: so are the barriers
+    const MhaSeq sq = {(long long)first * R + r, R, cnt};
+    for (int r0 = 0; r0 < cnt; r0 += MHA_WBLOCK)
+      mha_wide_rows<false, true>(q, k, v, q_ld, k_ld, v_ld, out, out_ld, col, hd, sq, r0 + wave * MHA_WROWS, scale, none, 0, 0, L,
+                                 L.Y);
+  }
+}
+
+// Pass 1 of the backward, wide: mha_bwd_rows_kernel's quantities for a block of MHA_WBLOCK query rows.  The scores and dA
+// accumulate over the chunks of K and of V; dQ leaves chunk by chunk.
+template <bool DROP>
+__global__ __launch_bounds__(256) void mha_wide_bwd_rows_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, const float* __restrict__ go,
+    int q_ld, int k_ld, int v_ld, int go_ld, float* __restrict__ gq, int gq_ld, float* __restrict__ ws, int S, int nhead,
+    int hd, long long seq_stride, long long batch_stride, const int* __restrict__ n_valid, float scale, MhaDrop dr) {
+  __shared__ MhaWideLds L;
+  const int n = blockIdx.x / nhead, h = blockIdx.x - n * nhead;
+  const int nv = n_valid ? min(*n_valid, S) : S;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if ((int)blockIdx.y * MHA_WBLOCK >= nv) return;
+  const int rw0 = blockIdx.y * MHA_WBLOCK + wave * MHA_WROWS;
+  const long long col = (long long)h * hd;
+  const MhaSeq sq = {n * batch_stride, seq_stride, nv};
+  float(*Pw)[MHA_SMAX] = L.P + wave * MHA_WROWS;
+  float* A = ws + (long long)blockIdx.x * 2 * S * S;
+  float* D = A + (long long)S * S;
+  float sc[MHA_WROWS][MHA_SMAX / 64] = {}, dp[MHA_WROWS][MHA_SMAX / 64] = {};
+  mha_wide_dots<true>(sc, q, q_ld, scale, k, k_ld, col, hd, sq, rw0, L, L.Y);
+  mha_wide_dots<true>(dp, go, go_ld, 1.f, v, v_ld, col, hd, sq, rw0, L, L.Y);
+#pragma unroll
+  for (int i = 0; i < MHA_WROWS; ++i) {
+    const int r = rw0 + i;
+    const uint64_t row_base = ((uint64_t)blockIdx.x * (uint64_t)S + (uint64_t)r) * (uint64_t)S;
+    bool keep[MHA_SMAX / 64];
+    float m = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) {
+      const int j = lane + 64 * t;
+      keep[t] = j < nv && r < nv && (DROP ? mha_keep(dr, row_base, j) : true);
+      if constexpr (DROP) dp[i][t] = keep[t] ? dp[i][t] * dr.drop_scale : 0.f;
+      m = fmaxf(m, j < nv ? sc[i][t] : -INFINITY);
+    }
+    m = nbm_wave_max(m);
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) {
+      sc[i][t] = (lane + 64 * t < nv) ? expf(sc[i][t] - m) : 0.f;
+      sum += sc[i][t];
+    }
+    sum = nbm_wave_sum(sum);
+    float dot = 0.f;
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) { sc[i][t] /= sum; dot = fmaf(sc[i][t], dp[i][t], dot); }
+    dot = nbm_wave_sum(dot);
+#pragma unroll
+    for (int t = 0; t < MHA_SMAX / 64; ++t) {
+      const int j = lane + 64 * t;
+      if (j < nv && r < nv) {
+        const float dsv = sc[i][t] * (dp[i][t] - dot);
+        Pw[i][j] = dsv;
+        A[(long long)r * S + j] = !DROP ? sc[i][t] : keep[t] ? sc[i][t] * dr.drop_scale : 0.f;
+        D[(long long)r * S + j] = dsv;
+      }
+    }
+  }
+  mha_wide_pv<true>(k, k_ld, col, hd, sq, L, L.Y, [&](int i, int c, float o) {
+    const int r = rw0 + i;
+    if (r < nv) gq[(sq.off + r * sq.stride) * gq_ld + col + c] = o * scale;
+  });
+}
+
+// Pass 2, wide: mha_bwd_keys_kernel with the columns and the key rows spread over the grid -- (entry, head) x 64-column chunk
+// x MHA_KEYBLOCKS interleaved sets of key rows.
+__global__ __launch_bounds__(256) void mha_wide_bwd_keys_kernel(
+    const float* __restrict__ q, const float* __restrict__ go, int q_ld, int go_ld, const float* __restrict__ ws,
+    float* __restrict__ gk, float* __restrict__ gv, int gk_ld, int gv_ld, int S, int nhead, int hd, long long seq_stride,
+    long long batch_stride, const int* __restrict__ n_valid, float scale) {
+  const int n = blockIdx.x / nhead, h = blockIdx.x - n * nhead;
+  const int nv = n_valid ? min(*n_valid, S) : S;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* A = ws + (long long)blockIdx.x * 2 * S * S;
+  const float* D = A + (long long)S * S;
+  const int c = blockIdx.y * 64 + lane;
+  if (c >= hd) return;
+  for (int j = blockIdx.z * 4 + wave; j < nv; j += 4 * MHA_KEYBLOCKS) {
+    float ak = 0.f, av = 0.f;
+    for (int r = 0; r < nv; ++r) {
+      const long long row = r * seq_stride + n * batch_stride;
+      ak = fmaf(D[(long long)r * S + j], q[row * q_ld + h * hd + c], ak);
+      av = fmaf(A[(long long)r * S + j], go[row * go_ld + h * hd + c], av);
+    }
+    const long long rowj = j * seq_stride + n * batch_stride;
+    gk[rowj * gk_ld + h * hd + c] = ak * scale;
+    gv[rowj * gv_ld + h * hd + c] = av;
+  }
+}
+
 // What the four nbm_mha_small* entry points ask of their geometry; pitches: every row pitch passed, each >= nhead * hd.
 bool mha_small_geometry_ok(int S, int N, int nhead, int hd, std::initializer_list<int> pitches) {
-  if (S <= 0 || S > MHA_SMAX || N <= 0 || nhead <= 0 || hd <= 0 || hd > MHA_HDMAX) return false;
+  if (S <= 0 || S > MHA_SMAX || N <= 0 || nhead <= 0 || hd <= 0 || hd > MHA_HDWIDE) return false;
   for (int ld : pitches)
     if (ld < nhead * hd) return false;
   return true;
@@ -310,8 +604,13 @@ int mha_small_launch(const float* q, const float* k, const float* v, int q_ld, i
                      int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid, float scale,
                      const MhaDrop& dr, void* stream) {
   if (!q || !k || !v || !out || !mha_small_geometry_ok(S, N, nhead, hd, {q_ld, k_ld, v_ld, out_ld})) return NBM_EINVAL;
-  hipLaunchKernelGGL(mha_small_kernel<DROP>, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out,
-                     out_ld, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid, scale, dr);
+  if (hd <= MHA_HDMAX)
+    hipLaunchKernelGGL(mha_small_kernel<DROP>, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out,
+                       out_ld, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid, scale, dr);
+  else
+    hipLaunchKernelGGL(mha_wide_small_kernel<DROP>, dim3(N * nhead, (S + MHA_WBLOCK - 1) / MHA_WBLOCK), dim3(256), 0,
+                       (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out, out_ld, S, nhead, hd, (long long)seq_stride,
+                       (long long)batch_stride, n_valid, scale, dr);
   return nbm_launch_status();
 }
 
@@ -322,11 +621,44 @@ int mha_small_bwd_launch(const float* q, const float* k, const float* v, const f
                          const MhaDrop& dr, void* stream) {
   if (!q || !k || !v || !go || !gq || !gk || !gv || !workspace) return NBM_EINVAL;
   if (!mha_small_geometry_ok(S, N, nhead, hd, {q_ld, k_ld, v_ld, go_ld, gq_ld, gk_ld, gv_ld})) return NBM_EINVAL;
-  hipLaunchKernelGGL(mha_bwd_rows_kernel<DROP>, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, go, q_ld, k_ld,
-                     v_ld, go_ld, gq, gq_ld, workspace, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid,
-                     scale, dr);
-  hipLaunchKernelGGL(mha_bwd_keys_kernel, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, go, q_ld, go_ld, workspace, gk,
-                     gv, gk_ld, gv_ld, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid, scale);
+  if (hd <= MHA_HDMAX) {
+    hipLaunchKernelGGL(mha_bwd_rows_kernel<DROP>, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, go, q_ld, k_ld,
+                       v_ld, go_ld, gq, gq_ld, workspace, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid,
+                       scale, dr);
+    hipLaunchKernelGGL(mha_bwd_keys_kernel, dim3(N * nhead), dim3(256), 0, (hipStream_t)stream, q, go, q_ld, go_ld, workspace, gk,
+                       gv, gk_ld, gv_ld, S, nhead, hd, (long long)seq_stride, (long long)batch_stride, n_valid, scale);
+  } else {
+    hipLaunchKernelGGL(mha_wide_bwd_rows_kernel<DROP>, dim3(N * nhead, (S + MHA_WBLOCK - 1) / MHA_WBLOCK), dim3(256), 0,
+                       (hipStream_t)stream, q, k, v, go, q_ld, k_ld, v_ld, go_ld, gq, gq_ld, workspace, S, nhead, hd,
+                       (long long)seq_stride, (long long)batch_stride, n_valid, scale, dr);
+    hipLaunchKernelGGL(mha_wide_bwd_keys_kernel, dim3(N * nhead, (hd + 63) / 64, MHA_KEYBLOCKS), dim3(256), 0,
+                       (hipStream_t)stream, q, go, q_ld, go_ld, workspace, gk, gv, gk_ld, gv_ld, S, nhead, hd,
+                       (long long)seq_stride, (long long)batch_stride, n_valid, scale);
+  }
+  return nbm_launch_status();
+}
+
+// nbm_mha_segments (hd_max = MHA_HDMAX) and nbm_mha_segments_wide (hd_max = MHA_HDWIDE): one argument check, one dispatch.
+int mha_segments_launch(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
+                        int B, int R, int nhead, int hd, int hd_max, int mode, const int32_t* segments, const int32_t* n_roi,
+                        int max_count, float scale, void* stream) {
+  if (!q || !k || !v || !out || !n_roi || B <= 0 || R <= 0 || nhead <= 0 || hd <= 0 || hd > hd_max) return NBM_EINVAL;
+  if (q_ld < nhead * hd || k_ld < nhead * hd || v_ld < nhead * hd || out_ld < nhead * hd) return NBM_EINVAL;
+  if (mode == NBM_MHA_ACROSS_ROIS) {
+    if (R > MHA_SMAX) return NBM_EINVAL;
+  } else if (mode == NBM_MHA_ACROSS_IMAGES) {
+    if (!segments || max_count < 1 || max_count > MHA_SMAX) return NBM_EINVAL;
+  } else {
+    return NBM_EINVAL;
+  }
+  if (hd <= MHA_HDMAX)
+    hipLaunchKernelGGL(mha_segments_kernel, dim3(B * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out,
+                       out_ld, B, R, nhead, hd, mode, segments, n_roi, max_count, scale);
+  else
+    hipLaunchKernelGGL(mha_wide_segments_kernel,
+                       dim3(B * nhead, mode == NBM_MHA_ACROSS_ROIS ? (R + MHA_WBLOCK - 1) / MHA_WBLOCK : 1), dim3(256), 0,
+                       (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out, out_ld, B, R, nhead, hd, mode, segments, n_roi,
+                       max_count, scale);
   return nbm_launch_status();
 }
 
@@ -368,16 +700,13 @@ extern "C" int nbm_mha_small_drop_bwd(const float* q, const float* k, const floa
 extern "C" int nbm_mha_segments(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out,
                                 int out_ld, int B, int R, int nhead, int hd, int mode, const int32_t* segments,
                                 const int32_t* n_roi, int max_count, float scale, void* stream) {
-  if (!q || !k || !v || !out || !n_roi || B <= 0 || R <= 0 || nhead <= 0 || hd <= 0 || hd > MHA_HDMAX) return NBM_EINVAL;
-  if (q_ld < nhead * hd || k_ld < nhead * hd || v_ld < nhead * hd || out_ld < nhead * hd) return NBM_EINVAL;
-  if (mode == NBM_MHA_ACROSS_ROIS) {
-    if (R > MHA_SMAX) return NBM_EINVAL;
-  } else if (mode == NBM_MHA_ACROSS_IMAGES) {
-    if (!segments || max_count < 1 || max_count > MHA_SMAX) return NBM_EINVAL;
-  } else {
-    return NBM_EINVAL;
-  }
-  hipLaunchKernelGGL(mha_segments_kernel, dim3(B * nhead), dim3(256), 0, (hipStream_t)stream, q, k, v, q_ld, k_ld, v_ld, out,
-                     out_ld, B, R, nhead, hd, mode, segments, n_roi, max_count, scale);
-  return nbm_launch_status();
+  return mha_segments_launch(q, k, v, q_ld, k_ld, v_ld, out, out_ld, B, R, nhead, hd, MHA_HDMAX, mode, segments, n_roi, max_count,
+                             scale, stream);
+}
+
+extern "C" int nbm_mha_segments_wide(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out,
+                                     int out_ld, int B, int R, int nhead, int hd, int mode, const int32_t* segments,
+                                     const int32_t* n_roi, int max_count, float scale, void* stream) {
+  return mha_segments_launch(q, k, v, q_ld, k_ld, v_ld, out, out_ld, B, R, nhead, hd, MHA_HDWIDE, mode, segments, n_roi, max_count,
+                             scale, stream);
 }

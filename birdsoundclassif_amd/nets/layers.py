@@ -334,8 +334,8 @@ class Transformer_RCNN(nn.Module):
         if not self.tf_pe_qk and E != 512:
             raise ValueError('the reference hard-codes d_model=512 for the non-pe_qk encoder (layers.py:619)')
         self.nhead = config.tf_nhead
-        if E % self.nhead or E // self.nhead > 64:
-            raise NotImplementedError('Transformer_RCNN: head dim must divide tf_model_dim and be <= 64')
+        if self.nhead < 1 or E % self.nhead or E // self.nhead > 512:    # csrc/mha.hip: MHA_HDWIDE
+            raise NotImplementedError('Transformer_RCNN: tf_nhead must divide tf_model_dim and the head dim be <= 512')
         self.pos_embedding = nn.Sequential(nn.Linear(in_dim, E), nn.LeakyReLU())
         self.rois_embedding = nn.Sequential(nn.Linear(in_dim, E), nn.LeakyReLU())
         self.encoder = _Encoder(E, self.nhead, config.tf_dim_feedforward, config.tf_num_encoder_layers)

@@ -847,7 +847,9 @@ def layernorm(x2d, w, b, eps=1e-5):
 
 
 def mha_small(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid=None):
-    """q, k, v: 2-D row views [S*N, >= E] (column slices of a fused projection are fine) -> out [S*N, E]."""
+    """q, k, v: 2-D row views [S*N, >= E] (column slices of a fused projection are fine) -> out [S*N, E].  S <= MHA_SMAX; any
+    head dim E // nhead <= 512 (csrc/mha.hip: one lane per column up to 64, chunked wide kernels above); the same holds for
+    `mha_segments`, `mha_small_drop` and the two backwards."""
     E = q.shape[1]
     hd = E // nhead
     for t in (q, k, v):
@@ -858,7 +860,7 @@ def mha_small(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid=None):
     return out
 
 
-MHA_SMAX = 128                  # csrc/mha.hip: longest sequence of nbm_mha_small / nbm_mha_segments
+MHA_SMAX = 128                  # csrc/mha.hip: longest sequence of nbm_mha_small / nbm_mha_segments / nbm_mha_segments_wide
 MHA_ACROSS_ROIS, MHA_ACROSS_IMAGES = 0, 1
 
 
@@ -881,9 +883,9 @@ def mha_segments(q, k, v, R, nhead, mode, segments, n_roi, max_count=None):
     _chk_counts(n_roi, B, 'n_roi')
     max_count = min(B, MHA_SMAX) if max_count is None else int(max_count)
     out = torch.empty((B * R, E), device=q.device, dtype=torch.float32)
-    check(lib().nbm_mha_segments(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(out), E, B, R, nhead, hd,
-                                 int(mode), _ptr(segments), _ptr(n_roi), max_count, 1.0 / math.sqrt(hd), _stream()),
-          'nbm_mha_segments')
+    check(lib().nbm_mha_segments_wide(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(out), E, B, R, nhead, hd,
+                                      int(mode), _ptr(segments), _ptr(n_roi), max_count, 1.0 / math.sqrt(hd), _stream()),
+          'nbm_mha_segments_wide')
     return out
 
 

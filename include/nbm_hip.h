@@ -487,10 +487,13 @@ int nbm_silu(const float* x, float* y, int64_t n, void* stream);
  * Transformer_RCNN head (reference layers.py:589-651, self_attention.py:110-131). */
 int nbm_layernorm(const float* x, int64_t rows, int E, const float* w, const float* b, float eps, float* y, void* stream);
 
-/* out = softmax(scale * Q K^T) V per (batch entry, head) for short sequences (S <= 128, hd <= 64): token (s, n) is row
+/* out = softmax(scale * Q K^T) V per (batch entry, head) for short sequences (S <= 128, hd <= 512): token (s, n) is row
  * s*seq_stride + n*batch_stride of q/k/v/out (row pitches *_ld floats, head h at columns [h*hd, (h+1)*hd)); keys with
  * s >= *n_valid (device counter, may be NULL) are masked -- nn.MultiheadAttention inside the Transformer_RCNN encoder
- * (reference layers.py:613-621,645-646; self_attention.py:110-126). */
+ * (reference layers.py:613-621,645-646; self_attention.py:110-126).  hd <= 64: one lane per output column, K and V of an
+ * (entry, head) whole in LDS; 64 < hd <= 512: the head dimension passes through LDS in 64-column chunks (csrc/mha.hip, "wide
+ * heads"); hd > 512 is NBM_EINVAL.  The same split and limit hold for the three entry points below that share this token layout and for
+ * nbm_mha_segments_wide. */
 int nbm_mha_small(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
                   int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                   float scale, void* stream);
@@ -501,6 +504,7 @@ int nbm_mha_small(const float* q, const float* k, const float* v, int q_ld, int 
  * not read.  ACROSS_IMAGES (default flavour, batch_first=False): per segment and slot r < n_roi[first], the sequence is the
  * segment's images.  EVERY row of `out` is written: rows that are no valid token (r >= n_roi, failed segments) are zero, so
  * the caller need not pre-fill.  A valid row holds the bits nbm_mha_small gives when it is run on that row's segment alone.
+ * hd <= 64 (callers rely on the refusal above it; nbm_mha_segments_wide below takes the wider heads).
  * max_count: the caller's bound on the table's segment counts (<= 128); the rows of a segment above it, or of an entry that
  * is no segment inside [0, B), are zero -- the per-segment model calls of the reference CLI (run_detection.py:49-55) through
  * layers.py:613-621,645-646. */
@@ -509,6 +513,11 @@ int nbm_mha_small(const float* q, const float* k, const float* v, int q_ld, int 
 int nbm_mha_segments(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
                      int B, int R, int nhead, int hd, int mode, const int32_t* segments, const int32_t* n_roi, int max_count,
                      float scale, void* stream);
+/* nbm_mha_segments for every head dim nbm_mha_small takes, 1 <= hd <= 512: the same arguments, checks and results; hd <= 64 is
+ * the launch nbm_mha_segments makes, above it the wide segments kernel (csrc/mha.hip).  hd > 512: NBM_EINVAL. */
+int nbm_mha_segments_wide(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
+                          int B, int R, int nhead, int hd, int mode, const int32_t* segments, const int32_t* n_roi,
+                          int max_count, float scale, void* stream);
 
 /* softmax over the (bg, fg) pair of every anchor: x[p][2a], x[p][2a+1] (pitch ld) -> y (pitch y_ld)
  * -- layers.py:90. */
@@ -776,7 +785,7 @@ int nbm_leaky_relu_bwd(const float* gy, const float* y, float* out, float slope,
 int nbm_layernorm_bwd(const float* x, const float* w, const float* g, int64_t rows, int E, float eps, float* gx, float* gw,
                       float* gb, void* stream);
 /* backward of nbm_mha_small: gq/gk/gv get every VALID token row written (pre-zero them when *n_valid < S);
- * workspace: 2*S*S floats per (batch entry, head) */
+ * workspace: 2*S*S floats per (batch entry, head), whatever hd (<= 512) */
 int nbm_mha_small_bwd(const float* q, const float* k, const float* v, const float* go, int q_ld, int k_ld, int v_ld,
                       int go_ld, float* gq, float* gk, float* gv, int gq_ld, int gk_ld, int gv_ld, float* workspace, int S,
                       int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
@@ -798,7 +807,7 @@ int nbm_mha_small_bwd(const float* q, const float* k, const float* v, const floa
 int nbm_dropout(const float* x, const float* residual, float* y, int64_t n, uint32_t threshold, float scale, uint64_t seed,
                 uint32_t call, uint32_t site_id, void* stream);
 /* nbm_mha_small with dropout on the softmax probabilities: A[r][j] = keep ? (e_j / sum) * drop_scale : 0, out = A V.  Token layout,
- * *n_valid handling, limits (S <= 128, hd <= 64) and argument checks are nbm_mha_small's.  The mask element of (batch entry n,
+ * *n_valid handling, limits (S <= 128, hd <= 512) and argument checks are nbm_mha_small's.  The mask element of (batch entry n,
  * head h, query r, key j) is ((n * nhead + h) * S + r) * S + j -- a dense [N][nhead][S][S] tensor, S the launch's S whatever
  * *n_valid holds.
  * Replaces: nn.MultiheadAttention(dropout=p) in training mode, self_attention.py:113,131 / layers.py:619-621. */
@@ -806,7 +815,7 @@ int nbm_mha_small_drop(const float* q, const float* k, const float* v, int q_ld,
                        int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                        float scale, uint32_t threshold, float drop_scale, uint64_t seed, uint32_t call, uint32_t site_id,
                        void* stream);
-/* backward of nbm_mha_small_drop (arguments and workspace of nbm_mha_small_bwd): dA = dO V^T, dP = keep ? dA * drop_scale : 0,
+/* backward of nbm_mha_small_drop (arguments, workspace and hd <= 512 of nbm_mha_small_bwd): dA = dO V^T, dP = keep ? dA * drop_scale : 0,
  * dS = P (dP - sum_j P dP), dQ = scale dS K, dK = scale dS^T Q, dV = A^T dO.
  * Replaces: autograd through nn.MultiheadAttention(dropout=p), train.py:212. */
 int nbm_mha_small_drop_bwd(const float* q, const float* k, const float* v, const float* go, int q_ld, int k_ld, int v_ld,
