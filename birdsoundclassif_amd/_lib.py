@@ -82,7 +82,8 @@ class BwdDesc(C.Structure):
                 ('kh', C.c_int), ('kw', C.c_int), ('stride', C.c_int), ('pad', C.c_int), ('Ho', C.c_int), ('Wo', C.c_int),
                 ('g_ld', C.c_int), ('w_ld', C.c_int), ('x_ld', C.c_int), ('out_ld', C.c_int), ('res_ld', C.c_int),
                 ('mask_ld', C.c_int), ('alpha', C.c_float), ('bias_grad', C.c_void_p), ('residual2', C.c_void_p), ('res2_ld', C.c_int),
-                ('mask_bits', C.c_void_p)]
+                ('mask_bits', C.c_void_p),
+                ('workspace', C.c_void_p), ('ws_split_stride', C.c_int64), ('workspace_bytes', C.c_int64)]
 
 
 class GemmPlan(C.Structure):
@@ -219,6 +220,25 @@ SIGNATURES = {
     'nbm_roi_pool_hw_bwd': [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     'nbm_sqnorm_accum': [_P, _L, _P, _P],
     'nbm_adamw_step': [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _I, _P, _F, _P],
+    # ---- deterministic twins (train.py --deterministic): the default entry point's arguments, then workspace, workspace_bytes
+    'nbm_conv_wgrad_workspace': [C.POINTER(BwdDesc), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    'nbm_det_workspace': [_I, _L, _I, C.POINTER(C.c_int64)],
+    'nbm_ordered_sum': [_P, _I, _I, _L, _P, _I, _P],
+    'nbm_colsum_det': [_P, _L, _I, _I, _P, _P, _L, _P],
+    'nbm_weighted_sum_bwd_det': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P],
+    'nbm_dwconv3x3_bwd_det': [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _L, _P],
+    'nbm_bn_train_fwd_det': [_P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    'nbm_bn_train_bwd_det': [_P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    'nbm_sqnorm_accum_det': [_P, _L, _P, _P, _L, _P],
+    'nbm_stem7x7_wgrad_workspace': [_I, _I, _I, C.POINTER(C.c_int64)],
+    'nbm_stem7x7_wgrad_det': [_P, _P, _I, _I, _I, _P, _P, _P, _L, _P],
+    'nbm_bias_grad_workspace': [_I, C.POINTER(C.c_int64)],
+    'nbm_wino_outgrad_det': [_P, _I, _I, _I, _I, _P, _P, _I, _P, _L, _P],
+    'nbm_wino23_outgrad_tiles_det': [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _P, _L, _P],
+    'nbm_cell_outgrad_det': [_P, _I, _I, _I, _I, _I, _P, _P, _P, _L, _P],
+    'nbm_cell_dgrad_output_det': [_P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P, _L, _P],
+    'nbm_roi_tiles_det': [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P],
+    'nbm_roi_pool_hw_bwd_det': [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _P, _P, _I, _I, _I, _I, _P, _P],
 }
 
 

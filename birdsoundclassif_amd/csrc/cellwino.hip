@@ -19,6 +19,7 @@
 // fp32 error against float64: 3e-6 relative (the F(2x2,3x3) level), measured in scripts / tests.
 // All three kernels are HBM-bound streams: a thread owns (cell, 4 channels), 16-byte accesses, channels fastest.
 #include "nbm_common.h"
+#include "nbm_ordered_sum.h"
 
 namespace {
 
@@ -46,6 +47,8 @@ __device__ __forceinline__ void cell_of(const CellGeom& q, unsigned cell, int& b
 // g [B][H][W][N] -> Vg [25][T][N] = E blk E^T per cell (pixels outside the image read as zeros); bias_grad (optional) +=
 // sum of the block pixels.  A thread keeps one channel quad over its grid-stride loop (the launch makes the stride a
 // multiple of N/4).
+// DET (this kernel and cell_dgrad_output_kernel): bias_grad is part[gridDim.x][N], see nbm_bias_slot_store.
+template <bool DET>
 __global__ __launch_bounds__(256) void cell_outgrad_kernel(const float* __restrict__ g, const CellGeom q, float* __restrict__ Vg,
                                                            float* __restrict__ bias_grad) {
   const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
@@ -85,7 +88,9 @@ __global__ __launch_bounds__(256) void cell_outgrad_kernel(const float* __restri
   }
   // bias gradient: per-thread sums -> LDS (one slot per channel) -> ONE global atomic per channel and workgroup.  (Per-thread global
   // atomics -- 8 M of them on 256 addresses -- were 2/3 of this kernel's time: 3.2 ms at 1.3 TB/s for 4.2 GB.)
-  if (bias_grad) {                     // uniform
+  if (DET) {
+    if (bias_grad) { const float bs[4] = {bsum[0], bsum[1], bsum[2], bsum[3]}; nbm_bias_slot_store<4>(bs, q.C4, bias_grad); }
+  } else if (bias_grad) {              // uniform
     __shared__ float red[MAX_BIAS_N];
     const int n = q.C4 * 4;
     for (int k = threadIdx.x; k < n; k += 256) red[k] = 0.f;
@@ -307,6 +312,7 @@ __global__ __launch_bounds__(256) void cell_patches_up_cols_kernel(const float* 
 // (cls < 0, S >= 5: patches of different cells do not overlap); the rest of gx is not touched.
 // cls = 0..3 (S >= 3): only the cells with (oy & 1, ox & 1) == (cls >> 1, cls & 1), and the patch is ADDED to gx -- cells of one
 // parity class are 2 S >= 6 pixels apart, so four launches accumulate the overlapping patches of a stride-3 / 4 pattern without atomics
+template <bool DET>
 __global__ __launch_bounds__(256) void cell_dgrad_output_kernel(const float* __restrict__ M, const CellGeom q, float* __restrict__ gx,
                                                                 int cls, int ld4, int coff4, float* __restrict__ bias_grad) {
   const f32x4* m4 = reinterpret_cast<const f32x4*>(M);
@@ -360,7 +366,9 @@ __global__ __launch_bounds__(256) void cell_dgrad_output_kernel(const float* __r
       }
     }
   }
-  if (bias_grad) {                     // uniform
+  if (DET) {
+    if (bias_grad) { const float bs[4] = {bsum[0], bsum[1], bsum[2], bsum[3]}; nbm_bias_slot_store<4>(bs, q.C4, bias_grad); }
+  } else if (bias_grad) {              // uniform
     __shared__ float red[MAX_BIAS_N];
     const int n = q.C4 * 4;
     for (int k = threadIdx.x; k < n; k += 256) red[k] = 0.f;
@@ -542,13 +550,30 @@ inline unsigned stream_grid(long long total, int per) {
 
 }  // namespace
 
-extern "C" int nbm_cell_outgrad(const float* g, int B, int H, int W, int N, int stride, float* Vg, float* bias_grad, void* stream) {
+// `workspace` NULL: the default bias flush (atomics); else the deterministic one (slots in `workspace`, added in order)
+static int cell_outgrad_impl(const float* g, int B, int H, int W, int N, int stride, float* Vg, float* bias_grad, float* workspace,
+                             long long workspace_bytes, void* stream) {
   CellGeom q;
   if (!g || !Vg || !cell_geom(B, H, W, N, stride, q)) return NBM_EINVAL;
   if (!nbm_aligned16(g) || !nbm_aligned16(Vg)) return NBM_EALIGN;
   if (bias_grad && N > MAX_BIAS_N) return NBM_EUNSUPPORTED;
-  hipLaunchKernelGGL(cell_outgrad_kernel, dim3(stream_grid(q.T * q.C4, q.C4)), dim3(256), 0, (hipStream_t)stream, g, q, Vg, bias_grad);
+  const unsigned blocks = stream_grid(q.T * q.C4, q.C4);
+  if (workspace && bias_grad) {
+    if (!nbm_bias_slots_fit(workspace, workspace_bytes, blocks, N)) return NBM_EINVAL;
+    hipLaunchKernelGGL(cell_outgrad_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, q, Vg, workspace);
+    nbm_ordered_sum_flat((const float*)workspace, (int)blocks, (long long)N, bias_grad, 1, (hipStream_t)stream);
+    return nbm_launch_status();
+  }
+  hipLaunchKernelGGL(cell_outgrad_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, q, Vg, bias_grad);
   return nbm_launch_status();
+}
+extern "C" int nbm_cell_outgrad(const float* g, int B, int H, int W, int N, int stride, float* Vg, float* bias_grad, void* stream) {
+  return cell_outgrad_impl(g, B, H, W, N, stride, Vg, bias_grad, nullptr, 0, stream);
+}
+extern "C" int nbm_cell_outgrad_det(const float* g, int B, int H, int W, int N, int stride, float* Vg, float* bias_grad, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  if (bias_grad && (!workspace || !nbm_aligned16(workspace))) return NBM_EINVAL;
+  return cell_outgrad_impl(g, B, H, W, N, stride, Vg, bias_grad, (float*)workspace, workspace_bytes, stream);
 }
 
 extern "C" int nbm_cell_input(const float* x, int B, int H, int W, int C, int stride, float* Vx, int ld, int c_off, void* stream) {
@@ -615,16 +640,33 @@ extern "C" int nbm_cell_output(const float* M, const float* bias, int B, int H, 
   return nbm_launch_status();
 }
 
-extern "C" int nbm_cell_dgrad_output(const float* M, int B, int H, int W, int C, int stride, float* gx, int parity_class, int ld,
-                                     int c_off, float* bias_grad, void* stream) {
+static int cell_dgrad_output_impl(const float* M, int B, int H, int W, int C, int stride, float* gx, int parity_class, int ld,
+                                  int c_off, float* bias_grad, float* workspace, long long workspace_bytes, void* stream) {
   CellGeom q;
   // parity_class < 0: 5x5 patches are WRITTEN, no overlap allowed (stride >= 5); 0..3: one parity class of cells, ADDED (stride >= 3)
   if (!M || !gx || parity_class > 3 || !cell_geom(B, H, W, C, stride, q, parity_class < 0 ? 5 : 3)) return NBM_EINVAL;
   if (ld < c_off + C || c_off < 0 || (ld & 3) || (c_off & 3) || (bias_grad && C > MAX_BIAS_N)) return NBM_EINVAL;
   if (!nbm_aligned16(M) || !nbm_aligned16(gx)) return NBM_EALIGN;
-  hipLaunchKernelGGL(cell_dgrad_output_kernel, dim3(stream_grid(q.T * q.C4, q.C4)), dim3(256), 0, (hipStream_t)stream, M, q, gx,
+  const unsigned blocks = stream_grid(q.T * q.C4, q.C4);
+  if (workspace && bias_grad) {
+    if (!nbm_bias_slots_fit(workspace, workspace_bytes, blocks, C)) return NBM_EINVAL;
+    hipLaunchKernelGGL(cell_dgrad_output_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, M, q, gx, parity_class, ld / 4,
+                       c_off / 4, workspace);
+    nbm_ordered_sum_flat((const float*)workspace, (int)blocks, (long long)C, bias_grad, 1, (hipStream_t)stream);
+    return nbm_launch_status();
+  }
+  hipLaunchKernelGGL(cell_dgrad_output_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, M, q, gx,
                      parity_class, ld / 4, c_off / 4, bias_grad);
   return nbm_launch_status();
+}
+extern "C" int nbm_cell_dgrad_output(const float* M, int B, int H, int W, int C, int stride, float* gx, int parity_class, int ld,
+                                     int c_off, float* bias_grad, void* stream) {
+  return cell_dgrad_output_impl(M, B, H, W, C, stride, gx, parity_class, ld, c_off, bias_grad, nullptr, 0, stream);
+}
+extern "C" int nbm_cell_dgrad_output_det(const float* M, int B, int H, int W, int C, int stride, float* gx, int parity_class, int ld,
+                                         int c_off, float* bias_grad, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (bias_grad && (!workspace || !nbm_aligned16(workspace))) return NBM_EINVAL;
+  return cell_dgrad_output_impl(M, B, H, W, C, stride, gx, parity_class, ld, c_off, bias_grad, (float*)workspace, workspace_bytes, stream);
 }
 
 extern "C" int nbm_cell_weight(const float* w, int N, int C, float* U_nc, int ld, float* U_cn, int ldt, void* stream) {

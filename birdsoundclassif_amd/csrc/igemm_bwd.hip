@@ -18,6 +18,7 @@
 #include "igemm_split_tn.h"
 #include "igemm_device.h"
 #include <type_traits>
+#include "nbm_ordered_sum.h"
 
 namespace {
 
@@ -53,6 +54,9 @@ struct BwdParams {
   // pixel grid, the stride, and the full grid again for the half-resolution residual
   nbm_fastdiv fd_hw[4], fd_w[4], fd_st, fd_HW, fd_W;
   nbm_fastdiv fd_howo, fd_wo;   // TN: output pixels per image, output row width
+  // TN, deterministic twin (DET instantiations only): split s STORES its scaled tile at ws + s * ws_stride + grp * N * ws_ld + n * ws_ld
+  // + col and its bias partial at ws + s * ws_stride + groups * N * ws_ld + grp * N + n; nbm_ordered_sum_launch adds the slices in split order
+  float* ws; long long ws_stride; int groups, ws_ld;
 };
 
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
@@ -440,7 +444,9 @@ enum { B_SAME = 0, B_STRIDED = 1, B_GENERIC = 2 };
 
 // BM: rows of the dW tile = output channels n of the convolution.  128 by default; 64 for layers with N <= 64 (ResNet layer1:
 // with the 128-row tile half of every MFMA multiplied the zero padding of the G tile -- 59 TF/s "executed" on 3x3 64 -> 64).
-template <int BN, int BMODE, int BM = 128>
+// DET: the deterministic twin (nbm_bwd_desc.workspace): same K loop, the epilogue stores into the split's own slice instead of adding
+// to dW / bias_grad with atomics.
+template <int BN, int BMODE, int BM = 128, bool DET = false>
 __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
   constexpr int WM = BM / 2, WN = BN / 2, MT = WM / 32, NT = WN / 32;
   constexpr int AP = BM + 4, BP = BN + 4;
@@ -663,9 +669,25 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
 
   if (do_bias) {
     const int n = bm0 + (tid % BM);
-    if (n < p.N) atomicAdd(p.bias_grad + (long long)grp * p.N + n, bsum);
+    if constexpr (DET) {
+      // (256 / BM threads hold shares of one column: added in thread order through LDS, then one store)
+      constexpr int BT = 256 / BM;
+      __syncthreads();
+      As[tid] = bsum;
+      __syncthreads();
+      if (tid < BM && n < p.N) {
+        float t = As[tid];
+#pragma unroll
+        for (int k = 1; k < BT; ++k) t += As[tid + k * BM];
+        p.ws[(long long)blockIdx.y * p.ws_stride + (long long)p.groups * p.N * p.ws_ld + (long long)grp * p.N + n] = t;
+      }
+    } else if (n < p.N) {
+      atomicAdd(p.bias_grad + (long long)grp * p.N + n, bsum);
+    }
   }
-  float* __restrict__ og = p.out + (long long)grp * p.out_gs;
+  float* __restrict__ og = DET ? p.ws + (long long)blockIdx.y * p.ws_stride + (long long)grp * p.N * p.ws_ld
+                               : p.out + (long long)grp * p.out_gs;
+  const int o_ld = DET ? p.ws_ld : p.out_ld;
 #pragma unroll
   for (int j = 0; j < NT; ++j) {
     const int jj = wn0 + j * 32 + lrow;
@@ -680,7 +702,8 @@ __global__ __launch_bounds__(256, 2) void igemm_tn_kernel(const BwdParams p) {
         if (n >= p.N) continue;
         float v = acc[i][j][e] * p.alpha;
         if (p.row_scale) v *= p.row_scale[n];
-        atomicAdd(og + (long long)n * p.out_ld + col, v);
+        if constexpr (DET) og[(long long)n * o_ld + col] = v;
+        else atomicAdd(og + (long long)n * o_ld + col, v);
       }
   }
 }
@@ -742,6 +765,14 @@ extern "C" int nbm_conv_dgrad(const nbm_bwd_desc* d, void* stream) {
   return nbm_launch_status();
 }
 
+extern "C" int nbm_conv_wgrad_workspace(const nbm_bwd_desc* d, int64_t* bytes, int64_t* split_stride) {
+  if (!d || !bytes) return NBM_EINVAL;
+  int rc = 0;
+  *bytes = wgrad_workspace_bytes(*d, read_gemm_switches(2), &rc);
+  if (!rc && split_stride) *split_stride = wgrad_slice_floats(*d);
+  return rc;
+}
+
 extern "C" int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream) {
   if (!d) return NBM_EINVAL;
   const GemmPlan pl = plan_wgrad(*d, read_gemm_switches(2));
@@ -773,6 +804,37 @@ extern "C" int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream) {
   p.b_generic = pl.b_generic;
   p.plain = pl.plain;
   p.k_chunk = pl.k_chunk;
+  if (d->workspace) {            // the deterministic twin: every split stores its slice, nbm_ordered_sum_launch adds them in split order
+    const long long slice = wgrad_slice_floats(*d);
+    if (d->ws_split_stride < slice || (d->ws_split_stride & 3)) return NBM_EINVAL;
+    if ((long long)pl.splits * d->ws_split_stride * 4 > d->workspace_bytes) return NBM_EINVAL;
+    if (!nbm_aligned16(d->workspace)) return NBM_EALIGN;
+    p.ws = d->workspace; p.ws_stride = d->ws_split_stride; p.groups = d->groups; p.ws_ld = wgrad_slice_ld(*d);
+    switch (pl.kernel) {
+      case K_TN_GENERIC: hipLaunchKernelGGL((igemm_tn_kernel<64, B_GENERIC, 128, true>), grid, block, 0, st, p); break;
+      case K_TN_128_SAME_M64: hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 64, true>), grid, block, 0, st, p); break;
+      case K_TN_128_STRIDED_M64: hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED, 64, true>), grid, block, 0, st, p); break;
+      case K_TN_64_SAME_M64: hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME, 64, true>), grid, block, 0, st, p); break;
+      case K_TN_64_STRIDED_M64: hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED, 64, true>), grid, block, 0, st, p); break;
+      case K_TN_128_SAME: hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 128, true>), grid, block, 0, st, p); break;
+      case K_TN_128_STRIDED: hipLaunchKernelGGL((igemm_tn_kernel<128, B_STRIDED, 128, true>), grid, block, 0, st, p); break;
+      case K_TN_64_SAME: hipLaunchKernelGGL((igemm_tn_kernel<64, B_SAME, 128, true>), grid, block, 0, st, p); break;
+      case K_TN_64_STRIDED: hipLaunchKernelGGL((igemm_tn_kernel<64, B_STRIDED, 128, true>), grid, block, 0, st, p); break;
+      default: return NBM_EINVAL;
+    }
+    OrderedSumShape s{};
+    s.slots = pl.splits; s.groups = d->groups; s.cols = d->kh * d->kw * d->Cin; s.accumulate = 1;
+    s.slot_stride = d->ws_split_stride; s.part_gs = (long long)d->N * p.ws_ld; s.part_ld = p.ws_ld; s.rows = d->N;
+    s.out_gs = d->out_gs; s.out_ld = d->out_ld;
+    nbm_ordered_sum_launch((const float*)d->workspace, d->out, s, st);
+    if (d->bias_grad) {              // the bias partials sit behind the dW rows of every slice
+      OrderedSumShape b{};
+      b.slots = pl.splits; b.groups = 1; b.cols = 1; b.accumulate = 1;
+      b.slot_stride = d->ws_split_stride; b.part_ld = 1; b.rows = (long long)d->groups * d->N; b.out_ld = 1;
+      nbm_ordered_sum_launch((const float*)d->workspace + (long long)d->groups * d->N * p.ws_ld, d->bias_grad, b, st);
+    }
+    return nbm_launch_status();
+  }
   switch (pl.kernel) {
     case K_TN_GENERIC: hipLaunchKernelGGL((igemm_tn_kernel<64, B_GENERIC>), grid, block, 0, st, p); break;
     case K_TN_128_SAME_M64: hipLaunchKernelGGL((igemm_tn_kernel<128, B_SAME, 64>), grid, block, 0, st, p); break;

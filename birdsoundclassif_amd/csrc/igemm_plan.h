@@ -310,7 +310,22 @@ inline void plan_splits(GemmPlan& pl, int M, int tiles, int slots, int rows_per_
   pl.splits = (M + pl.k_chunk - 1) / pl.k_chunk;
 }
 
-inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw) {
+// Deterministic twin of the weight gradient (nbm_bwd_desc.workspace): floats of one split's slice -- the dW rows of every
+// group, then the bias partials where a bias gradient rides -- and the ceiling on the whole workspace.  A plan
+// whose slices would exceed it gets fewer, longer splits (k_chunk grows to cover M with them): the grid then fills fewer of the chip's
+// rounds, which is the price.  best_split allows at most 16 rounds of 512 tiles of at most 128 x 128 floats, so the slices of one launch
+// never need more than 512 MB: the ceiling does not bind for any plan best_split makes and guards the arithmetic; one slice beyond it is
+// refused (NBM_EUNSUPPORTED).
+constexpr long long WGRAD_WS_MAX_BYTES = 1ll << 30;
+// (rows at their own pitch, taps * Cin rounded up to 4 floats -- not at out_ld: `out` may be a column slice of a much wider matrix, as the
+// attention's dV' / dK inside the [M][3 d] gradient of the fused projection, one group per image)
+inline int wgrad_slice_ld(const nbm_bwd_desc& d) { return (d.kh * d.kw * d.Cin + 3) / 4 * 4; }
+inline long long wgrad_slice_floats(const nbm_bwd_desc& d) {
+  return (long long)d.groups * d.N * wgrad_slice_ld(d) + (d.bias_grad ? ((long long)d.groups * d.N + 3) / 4 * 4 : 0);
+}
+
+// det: plan for the deterministic twin (what nbm_conv_wgrad does when d.workspace is set)
+inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw, bool det) {
   if (int rc = check_bwd_common(d)) return plan_error(rc);
   if (!d.x) return plan_error(NBM_EINVAL);
   if ((d.g_ld & 3) || (d.g_gs & 3) || !aligned16(d.g) || d.g_ld < ((d.N + 3) / 4) * 4) return plan_error(NBM_EALIGN);
@@ -327,7 +342,7 @@ inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw) {
   if (pl.plain && !pl.b_generic && d.Cin > 128 && (d.Cin & 127) == 64) {
     nbm_bwd_desc a = d;
     a.Cin = d.Cin - 64;
-    pl = plan_wgrad(a, sw);
+    pl = plan_wgrad(a, sw, det);
     pl.halves = 1;
     return pl;
   }
@@ -335,7 +350,7 @@ inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw) {
   // opt-in (NBM_SPLIT_BF16=1): plain weight-gradient GEMMs (1x1 convolutions, nn.Linear, the grouped Winograd- / cell-domain
   // products) with >= 192 rows and > 64 columns on the bf16 matrix pipe through split fp32 operands (igemm_split_tn.hip: 256 x 128 tiles).
   // Chosen by the LAYER, never by the number of pixels.  The bias gradient is not produced there (the caller sums the columns of G).
-  if (sw.split_bf16 && sw.split_tn && pl.plain && !pl.b_generic && !d.bias_grad && d.N >= SPLIT_TN_MIN_ROWS && d.Cin > 64 && d.out_ld >= d.Cin &&
+  if (!det && sw.split_bf16 && sw.split_tn && pl.plain && !pl.b_generic && !d.bias_grad && d.N >= SPLIT_TN_MIN_ROWS && d.Cin > 64 && d.out_ld >= d.Cin &&
       32ll * d.g_ld * 4 < TN_SPAN_MAX && 32ll * d.x_ld * 4 < TN_SPAN_MAX) {
     pl.m_tiles = (d.N + 255) / 256;
     pl.n_tiles = (d.Cin + 127) / 128;
@@ -354,6 +369,16 @@ inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw) {
   // or 4 workgroups per CU; sizing the rounds for 768 / 1024 was measured in round 5 and changes nothing -- 2.161 vs 2.155 ms on layer1's
   // 3x3: a CU with fewer workgroups left runs them faster, the matrix pipe is what they share -- scripts/wgrad_cycles.py, in the git history)
   plan_splits(pl, M, pl.m_tiles * pl.n_tiles * d.groups, 512, 8 * PLAN_BK);
+  if (det) {
+    const long long max_splits = WGRAD_WS_MAX_BYTES / (wgrad_slice_floats(d) * 4);
+    // one slice beyond the ceiling (a dW of more than 2^28 floats at its pitch): refused, never run on the default kernels instead
+    if (max_splits < 1) return plan_error(NBM_EUNSUPPORTED);
+    if (pl.splits > max_splits) {
+      const long long sp = max_splits;
+      pl.k_chunk = (int)(((M + sp - 1) / sp + PLAN_BK - 1) / PLAN_BK * PLAN_BK);
+      pl.splits = (M + pl.k_chunk - 1) / pl.k_chunk;
+    }
+  }
   const bool same = !pl.b_generic && d.stride == 1 && d.Ho == d.H && d.Wo == d.W && (d.Wo >= PLAN_BK || pl.plain) &&
                     (long long)PLAN_BK * d.x_ld * 4 < TN_SPAN_MAX;
   const int kernel = pl.b_generic ? K_TN_GENERIC
@@ -361,6 +386,28 @@ inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw) {
                                    : (wide ? (same ? K_TN_128_SAME : K_TN_128_STRIDED) : (same ? K_TN_64_SAME : K_TN_64_STRIDED));
   plan_kernel(pl, kernel, pl.m_tiles * pl.n_tiles, pl.splits, d.groups);
   return pl;
+}
+inline GemmPlan plan_wgrad(const nbm_bwd_desc& d, GemmSwitches sw) { return plan_wgrad(d, sw, d.workspace != nullptr); }
+
+// Bytes of the twin's workspace: splits x slice; 0 when one split sums every element and no bias gradient rides (the default kernel then
+// adds exactly one value per element, which no order can change).  Both calls of a `halves` plan use the same workspace in turn.
+inline long long wgrad_workspace_bytes(const nbm_bwd_desc& d, GemmSwitches sw, int* rc) {
+  const GemmPlan pl = plan_wgrad(d, sw, true);
+  *rc = pl.rc;
+  if (pl.rc) return 0;
+  if (pl.halves) {
+    nbm_bwd_desc a = d, b = d;
+    a.Cin = d.Cin - 64;
+    b.Cin = 64; b.x = d.x + (d.Cin - 64); b.out = d.out + (d.Cin - 64); b.bias_grad = nullptr;
+    // (both calls get the caller's one stride, the slice of the whole descriptor: the larger split count times that)
+    const GemmPlan pa = plan_wgrad(a, sw, true), pb = plan_wgrad(b, sw, true);
+    *rc = pa.rc ? pa.rc : pb.rc;
+    if (*rc) return 0;
+    const int na = (pa.splits <= 1 && !a.bias_grad) ? 0 : pa.splits, nb = pb.splits <= 1 ? 0 : pb.splits;
+    return (long long)(na > nb ? na : nb) * wgrad_slice_floats(d) * 4;
+  }
+  if (pl.splits <= 1 && !d.bias_grad) return 0;
+  return (long long)pl.splits * wgrad_slice_floats(d) * 4;
 }
 
 }  // namespace nbm_igemm

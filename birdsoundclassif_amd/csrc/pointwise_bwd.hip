@@ -3,6 +3,7 @@
 // RoI-pool gradient, and the fused clip-norm + AdamW step over flat parameter buffers.
 // All gather-form (deterministic) except where noted (weight-gradient and RoI reductions use fp32 atomics).
 #include "nbm_common.h"
+#include "nbm_ordered_sum.h"
 
 namespace {
 
@@ -121,6 +122,8 @@ __global__ void weighted_sum_kernel(const float* __restrict__ x0, const float* _
 }
 
 // gx_i = g relu(w_i)/den; gw_i += [w_i > 0] sum g (x_i - out)/den   (gw zeroed by the caller)
+//   DET: gw is part[gridDim.x][3]; every workgroup stores its three shares (zero where none), nbm_ordered_sum adds them in order
+template <bool DET>
 __global__ __launch_bounds__(256) void weighted_sum_bwd_kernel(const float* __restrict__ x0, const float* __restrict__ x1,
                                                                const float* __restrict__ x2, const float* __restrict__ wraw,
                                                                const float* __restrict__ g, float* __restrict__ gx0,
@@ -151,13 +154,20 @@ __global__ __launch_bounds__(256) void weighted_sum_bwd_kernel(const float* __re
   s0 = nbm_wave_sum(s0); s1 = nbm_wave_sum(s1); s2 = nbm_wave_sum(s2);
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s0; red[1][threadIdx.x >> 6] = s1; red[2][threadIdx.x >> 6] = s2; }
   __syncthreads();
-  if (threadIdx.x < 3 && (threadIdx.x < 2 || x2)) {
+  if (DET) {
+    if (threadIdx.x < 3) {
+      const float t = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+      gw[blockIdx.x * 3 + threadIdx.x] = ((threadIdx.x < 2 || x2) && wraw[threadIdx.x] > 0.f) ? t / den : 0.f;
+    }
+  } else if (threadIdx.x < 3 && (threadIdx.x < 2 || x2)) {
     const float t = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
     if (wraw[threadIdx.x] > 0.f) atomicAdd(gw + threadIdx.x, t / den);
   }
 }
 
 // out[n] += sum_m g[m][n]   (block partial sums in double, one atomic per column per block)
+//   DET: `out` is part[gridDim.x][N] in DOUBLE; every workgroup stores its column sums unrounded
+template <bool DET>
 __global__ void colsum_kernel(const float* __restrict__ g, long long M, int N, int ld, float* __restrict__ out) {
   const int n = blockIdx.y * 64 + (threadIdx.x & 63);
   const int sub = threadIdx.x >> 6;                      // 4 row lanes
@@ -167,7 +177,11 @@ __global__ void colsum_kernel(const float* __restrict__ g, long long M, int N, i
     for (long long m = blockIdx.x * 4ll + sub; m < M; m += (long long)gridDim.x * 4) acc += (double)g[m * ld + n];
   part[sub][threadIdx.x & 63] = acc;
   __syncthreads();
-  if (sub == 0 && n < N) atomicAdd(out + n, (float)(part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]));
+  if (sub == 0 && n < N) {
+    const double t = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    if (DET) reinterpret_cast<double*>(out)[(long long)blockIdx.x * N + n] = t;
+    else atomicAdd(out + n, (float)t);
+  }
 }
 
 // gradient of 3x3/s2/p1 max pooling, gather form over the arg-max positions the forward pass recorded (r*3+s, one byte
@@ -590,6 +604,8 @@ __global__ void dwconv_bwd_data_scatter_kernel(const float* __restrict__ g, int 
 }
 
 // depthwise 3x3 weight (+bias) gradient: one block column per output channel group, atomics on 9(+1) scalars
+//   DET (both forms): gw is part[gridDim.x][Cout][10] (nine taps, then the bias share), stored; gb unused
+template <bool DET>
 __global__ void dwconv_bwd_weight_kernel(const float* __restrict__ x, const float* __restrict__ g, int B, int H, int W,
                                          int Cin, int mult, int stride, float* __restrict__ gw, float* __restrict__ gb,
                                          int Ho, int Wo) {
@@ -627,6 +643,13 @@ __global__ void dwconv_bwd_weight_kernel(const float* __restrict__ x, const floa
   for (int e = 0; e < 10; ++e) part[sub][threadIdx.x & 63][e] = acc[e];
   __syncthreads();
   if (sub == 0 && o < Cout) {
+    if (DET) {
+      float* slot = gw + ((long long)blockIdx.x * Cout + o) * 10;
+#pragma unroll
+      for (int e = 0; e < 10; ++e)
+        slot[e] = part[0][threadIdx.x][e] + part[1][threadIdx.x][e] + part[2][threadIdx.x][e] + part[3][threadIdx.x][e];
+      return;
+    }
 #pragma unroll
     for (int e = 0; e < 9; ++e)
       atomicAdd(gw + o * 9 + e, part[0][threadIdx.x][e] + part[1][threadIdx.x][e] + part[2][threadIdx.x][e] + part[3][threadIdx.x][e]);
@@ -637,7 +660,7 @@ __global__ void dwconv_bwd_weight_kernel(const float* __restrict__ x, const floa
 // The same weight gradient, four consecutive output channels per thread (MULT in {1, 2, 4}): one 16-byte load of g and one
 // 16 / 8 / 4-byte load of x per tap and pixel instead of 4 + 4 x 9 scalar ones.  Same pixel partition per thread as the scalar
 // kernel (stream `sub` of block x), hence the same partial sums; 64 threads x 4 channels = 256 channels per block column.
-template <int MULT>
+template <int MULT, bool DET = false>
 __global__ __launch_bounds__(256) void dwconv_bwd_weight_vec_kernel(const float* __restrict__ x, const float* __restrict__ g, int B,
                                                                     int H, int W, int Cin, int stride, float* __restrict__ gw,
                                                                     float* __restrict__ gb, int Ho, int Wo) {
@@ -706,6 +729,13 @@ __global__ __launch_bounds__(256) void dwconv_bwd_weight_vec_kernel(const float*
   if (sub == 0 && o0 < Cout) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+      if (DET) {
+        float* slot = gw + ((long long)blockIdx.x * Cout + o0 + j) * 10;
+#pragma unroll
+        for (int e = 0; e < 10; ++e)
+          slot[e] = part[0][lane][j * 10 + e] + part[1][lane][j * 10 + e] + part[2][lane][j * 10 + e] + part[3][lane][j * 10 + e];
+        continue;
+      }
 #pragma unroll
       for (int e = 0; e < 9; ++e)
         atomicAdd(gw + (o0 + j) * 9 + e, part[0][lane][j * 10 + e] + part[1][lane][j * 10 + e] + part[2][lane][j * 10 + e] + part[3][lane][j * 10 + e]);
@@ -738,7 +768,8 @@ __global__ void film_bwd_kernel(const float* __restrict__ gy, const float* __res
 }
 
 // ---- train-mode BatchNorm over [M][C] (per-channel statistics over the M rows)
-// pass 1: sums in double -> stats[c] = {sum, sumsq}
+// pass 1: sums in double -> stats[c] = {sum, sumsq}   (DET: stats is part[gridDim.x][C][2], stored)
+template <bool DET>
 __global__ void bn_stats_kernel(const float* __restrict__ x, long long M, int C, double* __restrict__ stats) {
   const int c = blockIdx.y * 64 + (threadIdx.x & 63);
   const int sub = threadIdx.x >> 6;
@@ -752,8 +783,10 @@ __global__ void bn_stats_kernel(const float* __restrict__ x, long long M, int C,
   ps[sub][threadIdx.x & 63] = s; pq[sub][threadIdx.x & 63] = q;
   __syncthreads();
   if (sub == 0 && c < C) {
-    atomicAdd(stats + 2 * c, ps[0][threadIdx.x] + ps[1][threadIdx.x] + ps[2][threadIdx.x] + ps[3][threadIdx.x]);
-    atomicAdd(stats + 2 * c + 1, pq[0][threadIdx.x] + pq[1][threadIdx.x] + pq[2][threadIdx.x] + pq[3][threadIdx.x]);
+    const double ts = ps[0][threadIdx.x] + ps[1][threadIdx.x] + ps[2][threadIdx.x] + ps[3][threadIdx.x];
+    const double tq = pq[0][threadIdx.x] + pq[1][threadIdx.x] + pq[2][threadIdx.x] + pq[3][threadIdx.x];
+    if (DET) { double* slot = stats + ((long long)blockIdx.x * C + c) * 2; slot[0] = ts; slot[1] = tq; }
+    else { atomicAdd(stats + 2 * c, ts); atomicAdd(stats + 2 * c + 1, tq); }
   }
 }
 // finalize: mean, invstd; running stats update (momentum, unbiased variance) -- nn.BatchNorm2d semantics
@@ -782,7 +815,8 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, long long M, int C,
     y[i] = (x[i] - mean[c]) * invstd[c] * w[c] + b[c];
   }
 }
-// backward pass 1: red[c] = {sum g, sum g*xhat}
+// backward pass 1: red[c] = {sum g, sum g*xhat}   (DET: red is part[gridDim.x][C][2], stored)
+template <bool DET>
 __global__ void bn_bwd_reduce_kernel(const float* __restrict__ g, const float* __restrict__ x, long long M, int C,
                                      const float* __restrict__ mean, const float* __restrict__ invstd,
                                      double* __restrict__ red) {
@@ -800,8 +834,10 @@ __global__ void bn_bwd_reduce_kernel(const float* __restrict__ g, const float* _
   ps[sub][threadIdx.x & 63] = s; pq[sub][threadIdx.x & 63] = q;
   __syncthreads();
   if (sub == 0 && c < C) {
-    atomicAdd(red + 2 * c, ps[0][threadIdx.x] + ps[1][threadIdx.x] + ps[2][threadIdx.x] + ps[3][threadIdx.x]);
-    atomicAdd(red + 2 * c + 1, pq[0][threadIdx.x] + pq[1][threadIdx.x] + pq[2][threadIdx.x] + pq[3][threadIdx.x]);
+    const double ts = ps[0][threadIdx.x] + ps[1][threadIdx.x] + ps[2][threadIdx.x] + ps[3][threadIdx.x];
+    const double tq = pq[0][threadIdx.x] + pq[1][threadIdx.x] + pq[2][threadIdx.x] + pq[3][threadIdx.x];
+    if (DET) { double* slot = red + ((long long)blockIdx.x * C + c) * 2; slot[0] = ts; slot[1] = tq; }
+    else { atomicAdd(red + 2 * c, ts); atomicAdd(red + 2 * c + 1, tq); }
   }
 }
 // backward pass 2: gx = w*invstd*(g - sum_g/M - xhat*sum_gxhat/M); gw = sum_gxhat, gb = sum_g
@@ -912,6 +948,8 @@ __global__ void tiles_upsample_bwd_add_kernel(const float* __restrict__ compact,
 }
 
 // ---- optimiser: squared gradient norm, then clip + AdamW (torch.optim.AdamW semantics, decoupled decay)
+//   DET: out is part[gridDim.x], stored
+template <bool DET>
 __global__ void sqnorm_kernel(const float* __restrict__ g, long long n, double* __restrict__ out) {
   double acc = 0.0;
   GRID_STRIDE(i, n) { const double v = (double)g[i]; acc += v * v; }
@@ -920,7 +958,12 @@ __global__ void sqnorm_kernel(const float* __restrict__ g, long long n, double* 
   __shared__ double part[TPB / 64];
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) { double s = 0.0; for (int i = 0; i < TPB / 64; ++i) s += part[i]; atomicAdd(out, s); }
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < TPB / 64; ++i) s += part[i];
+    if (DET) out[blockIdx.x] = s;
+    else atomicAdd(out, s);
+  }
 }
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                              float* __restrict__ v, long long n, float lr, float beta1, float beta2, float eps, float wd,
@@ -945,6 +988,44 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 }  // namespace
 
 #define ST ((hipStream_t)stream)
+
+// ---- deterministic twins: the grids of the reductions below, stated once for the launches and for nbm_det_workspace
+namespace {
+inline int colsum_blocks(long long M) { return grid_for(M, 4, 1024); }                 // also the BatchNorm reductions
+inline int sqnorm_blocks(long long n) { return grid_for(n, TPB, 2048); }
+inline int wsum_blocks(long long n) { return grid_for(n / 4, TPB, 2048); }
+inline int dwconv_wgrad_blocks(long long npix) { return grid_for(npix, 4, 192); }
+inline long long det_bytes(int op, long long rows, int cols) {
+  switch (op) {
+    case NBM_DET_COLSUM: return (long long)colsum_blocks(rows) * cols * 8;
+    case NBM_DET_SQNORM: return (long long)sqnorm_blocks(rows) * 8;
+    case NBM_DET_BN: return (long long)colsum_blocks(rows) * cols * 16;
+    case NBM_DET_WEIGHTED_SUM: return (long long)wsum_blocks(rows) * 12;
+    case NBM_DET_DWCONV: return (long long)dwconv_wgrad_blocks(rows) * cols * 40;
+    default: return -1;
+  }
+}
+// a twin's workspace: present, 16-byte aligned, large enough
+inline int det_ws_check(const void* ws, long long have, long long need) {
+  if (!ws || need < 0 || have < need) return NBM_EINVAL;
+  return nbm_aligned16(ws) ? NBM_OK : NBM_EALIGN;
+}
+}  // namespace
+
+extern "C" int nbm_det_workspace(int op, int64_t rows, int cols, int64_t* bytes) {
+  if (!bytes || rows <= 0 || cols <= 0) return NBM_EINVAL;
+  const long long b = det_bytes(op, (long long)rows, cols);
+  if (b < 0) return NBM_EINVAL;
+  *bytes = (b + 15) / 16 * 16;
+  return NBM_OK;
+}
+
+extern "C" int nbm_ordered_sum(const void* part, int part_is_double, int slots, int64_t n, float* out, int accumulate, void* stream) {
+  if (!part || !out || slots <= 0 || n <= 0) return NBM_EINVAL;
+  if (part_is_double) nbm_ordered_sum_flat((const double*)part, slots, (long long)n, out, accumulate, ST);
+  else nbm_ordered_sum_flat((const float*)part, slots, (long long)n, out, accumulate, ST);
+  return nbm_launch_status();
+}
 
 // gradient of nbm_avgpool2x2: every pixel of a 2x2 block receives a quarter of the block's gradient
 __global__ void avgpool2x2_bwd_kernel(const float* __restrict__ gy, int B, int Ho, int Wo, int C4, float* __restrict__ gx) {
@@ -1025,16 +1106,38 @@ extern "C" int nbm_weighted_sum(const float* x0, const float* x1, const float* x
 extern "C" int nbm_weighted_sum_bwd(const float* x0, const float* x1, const float* x2, const float* weights, const float* g,
                                     float* gx0, float* gx1, float* gx2, float* gw, int64_t n, void* stream) {
   if (!x0 || !x1 || !weights || !g || !gw || n <= 0 || (n & 3)) return NBM_EINVAL;
-  hipLaunchKernelGGL(weighted_sum_bwd_kernel, dim3(grid_for(n / 4, TPB, 2048)), dim3(256), 0, ST, x0, x1, x2, weights, g, gx0,
+  hipLaunchKernelGGL(weighted_sum_bwd_kernel<false>, dim3(wsum_blocks(n)), dim3(256), 0, ST, x0, x1, x2, weights, g, gx0,
                      gx1, gx2, gw, (long long)(n / 4));
+  return nbm_launch_status();
+}
+extern "C" int nbm_weighted_sum_bwd_det(const float* x0, const float* x1, const float* x2, const float* weights, const float* g,
+                                        float* gx0, float* gx1, float* gx2, float* gw, int64_t n, void* workspace,
+                                        int64_t workspace_bytes, void* stream) {
+  if (!x0 || !x1 || !weights || !g || !gw || n <= 0 || (n & 3)) return NBM_EINVAL;
+  if (int rc = det_ws_check(workspace, workspace_bytes, det_bytes(NBM_DET_WEIGHTED_SUM, n, 1))) return rc;
+  const int blocks = wsum_blocks(n);
+  hipLaunchKernelGGL(weighted_sum_bwd_kernel<true>, dim3(blocks), dim3(256), 0, ST, x0, x1, x2, weights, g, gx0, gx1, gx2,
+                     (float*)workspace, (long long)(n / 4));
+  OrderedSumShape s{};                // slots of 3 floats; gw holds 2 without x2
+  s.slots = blocks; s.groups = 1; s.cols = 1; s.accumulate = 1; s.slot_stride = 3; s.part_ld = 1; s.rows = x2 ? 3 : 2; s.out_ld = 1;
+  nbm_ordered_sum_launch((const float*)workspace, gw, s, ST);
   return nbm_launch_status();
 }
 extern "C" int nbm_colsum(const float* g, int64_t M, int N, int ld, float* out, void* stream) {
   if (!g || !out || M <= 0 || N <= 0 || ld < N) return NBM_EINVAL;
   hipError_t e = nbm_zero_async(out, sizeof(float) * N, ST);
   if (e != hipSuccess) return (int)e;
-  dim3 grid(grid_for(M, 4, 1024), (N + 63) / 64);
-  hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, ST, g, (long long)M, N, ld, out);
+  dim3 grid(colsum_blocks(M), (N + 63) / 64);
+  hipLaunchKernelGGL(colsum_kernel<false>, grid, dim3(256), 0, ST, g, (long long)M, N, ld, out);
+  return nbm_launch_status();
+}
+extern "C" int nbm_colsum_det(const float* g, int64_t M, int N, int ld, float* out, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+  if (!g || !out || M <= 0 || N <= 0 || ld < N) return NBM_EINVAL;
+  if (int rc = det_ws_check(workspace, workspace_bytes, det_bytes(NBM_DET_COLSUM, M, N))) return rc;
+  dim3 grid(colsum_blocks(M), (N + 63) / 64);
+  hipLaunchKernelGGL(colsum_kernel<true>, grid, dim3(256), 0, ST, g, (long long)M, N, ld, (float*)workspace);
+  nbm_ordered_sum_flat((const double*)workspace, (int)grid.x, N, out, 0, ST);
   return nbm_launch_status();
 }
 extern "C" int nbm_maxpool3x3s2_bwd(const uint8_t* idx, const float* gy, float* gx, int B, int H, int W, int C, int Ho,
@@ -1088,8 +1191,9 @@ extern "C" int nbm_pair_softmax_bwd(const float* y, const float* gy, float* gx, 
   hipLaunchKernelGGL(pair_softmax_bwd_kernel, dim3(grid_for(n_pairs)), dim3(TPB), 0, ST, y, gy, gx, (long long)n_pairs);
   return nbm_launch_status();
 }
-extern "C" int nbm_dwconv3x3_bwd(const float* x, const float* g, const float* w, int B, int H, int W, int Cin, int mult,
-                                 int stride, float* gx, float* gw, float* gb, int Ho, int Wo, void* stream) {
+// `workspace` NULL: the default kernels (atomics); else the deterministic twin of the weight gradient (nbm_dwconv3x3_bwd_det)
+static int dwconv3x3_bwd_impl(const float* x, const float* g, const float* w, int B, int H, int W, int Cin, int mult,
+                              int stride, float* gx, float* gw, float* gb, int Ho, int Wo, float* workspace, void* stream) {
   if (!x || !g || !w || B <= 0 || Cin <= 0 || mult <= 0 || stride <= 0) return NBM_EINVAL;
   if ((H + 2 - 3) / stride + 1 != Ho || (W + 2 - 3) / stride + 1 != Wo) return NBM_EINVAL;
   const int Cout = Cin * mult;
@@ -1103,14 +1207,30 @@ extern "C" int nbm_dwconv3x3_bwd(const float* x, const float* g, const float* w,
     else hipLaunchKernelGGL(dwconv_bwd_data_kernel<0>, grid, dim3(TPB), 0, ST, g, B, H, W, Cin, mult, stride, w, gx, Ho, Wo, 0);
   }
   if (gw) {
+    // 192 workgroup columns: every workgroup ends with 2560 atomics on the same 5120 addresses, and that tail grows with the grid
+    // (B = 128, 24 x 64 outputs, 512 channels: 64 -> 0.75, 128 -> 0.48, 192 -> 0.44, 256 -> 0.47, 512 -> 0.63, 1024 -> 0.86 ms)
+    dim3 grid(dwconv_wgrad_blocks((long long)B * Ho * Wo), (Cout + 63) / 64);
+    const bool vec = (mult == 1 || mult == 2 || mult == 4) && (Cout & 3) == 0 && (Cin % (4 / mult)) == 0 && nbm_aligned16(g) &&
+                     nbm_aligned16(x) && (long long)B * Ho * Wo < (1ll << 31) - 4ll * 65536;
+    if (workspace) {                 // part[grid.x][Cout][10]: every slot is stored by its workgroup, then added in slot order
+      const dim3 gv(grid.x, (Cout + 255) / 256);
+      if (vec && mult == 1) hipLaunchKernelGGL((dwconv_bwd_weight_vec_kernel<1, true>), gv, dim3(256), 0, ST, x, g, B, H, W, Cin, stride, workspace, gb, Ho, Wo);
+      else if (vec && mult == 2) hipLaunchKernelGGL((dwconv_bwd_weight_vec_kernel<2, true>), gv, dim3(256), 0, ST, x, g, B, H, W, Cin, stride, workspace, gb, Ho, Wo);
+      else if (vec) hipLaunchKernelGGL((dwconv_bwd_weight_vec_kernel<4, true>), gv, dim3(256), 0, ST, x, g, B, H, W, Cin, stride, workspace, gb, Ho, Wo);
+      else hipLaunchKernelGGL(dwconv_bwd_weight_kernel<true>, grid, dim3(256), 0, ST, x, g, B, H, W, Cin, mult, stride, workspace, gb, Ho, Wo);
+      OrderedSumShape s{};
+      s.slots = (int)grid.x; s.groups = 1; s.slot_stride = (long long)Cout * 10; s.part_ld = 10; s.rows = Cout;
+      s.cols = 9; s.out_ld = 9;
+      nbm_ordered_sum_launch((const float*)workspace, gw, s, ST);
+      if (gb) {
+        s.cols = 1; s.out_ld = 1;
+        nbm_ordered_sum_launch((const float*)workspace + 9, gb, s, ST);
+      }
+      return nbm_launch_status();
+    }
     hipError_t e = nbm_zero_async(gw, sizeof(float) * Cout * 9, ST);
     if (e == hipSuccess && gb) e = nbm_zero_async(gb, sizeof(float) * Cout, ST);
     if (e != hipSuccess) return (int)e;
-    // 192 workgroup columns: every workgroup ends with 2560 atomics on the same 5120 addresses, and that tail grows with the grid
-    // (B = 128, 24 x 64 outputs, 512 channels: 64 -> 0.75, 128 -> 0.48, 192 -> 0.44, 256 -> 0.47, 512 -> 0.63, 1024 -> 0.86 ms)
-    dim3 grid(grid_for((long long)B * Ho * Wo, 4, 192), (Cout + 63) / 64);
-    const bool vec = (mult == 1 || mult == 2 || mult == 4) && (Cout & 3) == 0 && (Cin % (4 / mult)) == 0 && nbm_aligned16(g) &&
-                     nbm_aligned16(x) && (long long)B * Ho * Wo < (1ll << 31) - 4ll * 65536;
     if (vec) {
       const dim3 gv(grid.x, (Cout + 255) / 256);
       if (mult == 1) hipLaunchKernelGGL(dwconv_bwd_weight_vec_kernel<1>, gv, dim3(256), 0, ST, x, g, B, H, W, Cin, stride, gw, gb, Ho, Wo);
@@ -1118,9 +1238,20 @@ extern "C" int nbm_dwconv3x3_bwd(const float* x, const float* g, const float* w,
       else hipLaunchKernelGGL(dwconv_bwd_weight_vec_kernel<4>, gv, dim3(256), 0, ST, x, g, B, H, W, Cin, stride, gw, gb, Ho, Wo);
       return nbm_launch_status();
     }
-    hipLaunchKernelGGL(dwconv_bwd_weight_kernel, grid, dim3(256), 0, ST, x, g, B, H, W, Cin, mult, stride, gw, gb, Ho, Wo);
+    hipLaunchKernelGGL(dwconv_bwd_weight_kernel<false>, grid, dim3(256), 0, ST, x, g, B, H, W, Cin, mult, stride, gw, gb, Ho, Wo);
   }
   return nbm_launch_status();
+}
+extern "C" int nbm_dwconv3x3_bwd(const float* x, const float* g, const float* w, int B, int H, int W, int Cin, int mult,
+                                 int stride, float* gx, float* gw, float* gb, int Ho, int Wo, void* stream) {
+  return dwconv3x3_bwd_impl(x, g, w, B, H, W, Cin, mult, stride, gx, gw, gb, Ho, Wo, nullptr, stream);
+}
+extern "C" int nbm_dwconv3x3_bwd_det(const float* x, const float* g, const float* w, int B, int H, int W, int Cin, int mult,
+                                     int stride, float* gx, float* gw, float* gb, int Ho, int Wo, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || mult <= 0) return NBM_EINVAL;
+  if (int rc = det_ws_check(workspace, workspace_bytes, det_bytes(NBM_DET_DWCONV, (long long)B * Ho * Wo, Cin * mult))) return rc;
+  return dwconv3x3_bwd_impl(x, g, w, B, H, W, Cin, mult, stride, gx, gw, gb, Ho, Wo, (float*)workspace, stream);
 }
 // Data gradient of the depthwise 3x3 ADDED into gx -- see nbm_hip.h.
 extern "C" int nbm_dwconv3x3_bwd_acc(const float* g, const float* w, int B, int H, int W, int Cin, int mult, int stride,
@@ -1153,29 +1284,63 @@ extern "C" int nbm_film_bwd(const float* gy, const float* z, const float* film, 
   hipLaunchKernelGGL(film_bwd_kernel, dim3(grid_for(n_pix * C)), dim3(TPB), 0, ST, gy, z, film, gz, gfilm, (long long)n_pix, C);
   return nbm_launch_status();
 }
-extern "C" int nbm_bn_train_fwd(const float* x, int64_t M, int C, const float* w, const float* b, float eps,
-                                float momentum, float* run_mean, float* run_var, double* stats_ws, float* mean,
-                                float* invstd, float* y, void* stream) {
+// `part` NULL: the default reduction (double atomics into the zeroed stats_ws); else part[blocks][C][2], added in block order
+static int bn_train_fwd_impl(const float* x, int64_t M, int C, const float* w, const float* b, float eps,
+                             float momentum, float* run_mean, float* run_var, double* stats_ws, float* mean,
+                             float* invstd, float* y, double* part, void* stream) {
   if (!x || !w || !b || !stats_ws || !mean || !invstd || !y || M <= 0 || C <= 0) return NBM_EINVAL;
-  hipError_t e = nbm_zero_async(stats_ws, sizeof(double) * 2 * C, ST);
-  if (e != hipSuccess) return (int)e;
-  dim3 grid(grid_for(M, 4, 1024), (C + 63) / 64);
-  hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, ST, x, (long long)M, C, stats_ws);
+  dim3 grid(colsum_blocks(M), (C + 63) / 64);
+  if (part) {
+    hipLaunchKernelGGL(bn_stats_kernel<true>, grid, dim3(256), 0, ST, x, (long long)M, C, part);
+    nbm_ordered_sum_flat((const double*)part, (int)grid.x, 2ll * C, stats_ws, 0, ST);
+  } else {
+    hipError_t e = nbm_zero_async(stats_ws, sizeof(double) * 2 * C, ST);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(bn_stats_kernel<false>, grid, dim3(256), 0, ST, x, (long long)M, C, stats_ws);
+  }
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(64), 0, ST, stats_ws, (long long)M, C, eps, momentum,
                      mean, invstd, run_mean, run_var);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(M * C)), dim3(TPB), 0, ST, x, (long long)M, C, mean, invstd, w, b, y);
   return nbm_launch_status();
 }
-extern "C" int nbm_bn_train_bwd(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd,
-                                const float* w, double* red_ws, float* gx, float* gw, float* gb, void* stream) {
+extern "C" int nbm_bn_train_fwd(const float* x, int64_t M, int C, const float* w, const float* b, float eps,
+                                float momentum, float* run_mean, float* run_var, double* stats_ws, float* mean,
+                                float* invstd, float* y, void* stream) {
+  return bn_train_fwd_impl(x, M, C, w, b, eps, momentum, run_mean, run_var, stats_ws, mean, invstd, y, nullptr, stream);
+}
+extern "C" int nbm_bn_train_fwd_det(const float* x, int64_t M, int C, const float* w, const float* b, float eps,
+                                    float momentum, float* run_mean, float* run_var, double* stats_ws, float* mean,
+                                    float* invstd, float* y, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (M <= 0 || C <= 0) return NBM_EINVAL;
+  if (int rc = det_ws_check(workspace, workspace_bytes, det_bytes(NBM_DET_BN, M, C))) return rc;
+  return bn_train_fwd_impl(x, M, C, w, b, eps, momentum, run_mean, run_var, stats_ws, mean, invstd, y, (double*)workspace, stream);
+}
+static int bn_train_bwd_impl(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd,
+                             const float* w, double* red_ws, float* gx, float* gw, float* gb, double* part, void* stream) {
   if (!g || !x || !mean || !invstd || !w || !red_ws || !gx || !gw || !gb || M <= 0 || C <= 0 || M * (int64_t)C < C) return NBM_EINVAL;
-  hipError_t e = nbm_zero_async(red_ws, sizeof(double) * 2 * C, ST);
-  if (e != hipSuccess) return (int)e;
-  dim3 grid(grid_for(M, 4, 1024), (C + 63) / 64);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(256), 0, ST, g, x, (long long)M, C, mean, invstd, red_ws);
+  dim3 grid(colsum_blocks(M), (C + 63) / 64);
+  if (part) {
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(256), 0, ST, g, x, (long long)M, C, mean, invstd, part);
+    nbm_ordered_sum_flat((const double*)part, (int)grid.x, 2ll * C, red_ws, 0, ST);
+  } else {
+    hipError_t e = nbm_zero_async(red_ws, sizeof(double) * 2 * C, ST);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(256), 0, ST, g, x, (long long)M, C, mean, invstd, red_ws);
+  }
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(M * C)), dim3(TPB), 0, ST, g, x, (long long)M, C, mean, invstd, w,
                      red_ws, gx, gw, gb);
   return nbm_launch_status();
+}
+extern "C" int nbm_bn_train_bwd(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd,
+                                const float* w, double* red_ws, float* gx, float* gw, float* gb, void* stream) {
+  return bn_train_bwd_impl(g, x, M, C, mean, invstd, w, red_ws, gx, gw, gb, nullptr, stream);
+}
+extern "C" int nbm_bn_train_bwd_det(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd,
+                                    const float* w, double* red_ws, float* gx, float* gw, float* gb, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  if (M <= 0 || C <= 0) return NBM_EINVAL;
+  if (int rc = det_ws_check(workspace, workspace_bytes, det_bytes(NBM_DET_BN, M, C))) return rc;
+  return bn_train_bwd_impl(g, x, M, C, mean, invstd, w, red_ws, gx, gw, gb, (double*)workspace, stream);
 }
 extern "C" int nbm_zero_pattern(float* g, int B, int H, int W, int C, int stride, void* stream) {
   if (!g || B <= 0 || B > 65535 || H <= 0 || W <= 0 || C <= 0 || (C & 3) || stride < 1) return NBM_EINVAL;
@@ -1209,7 +1374,15 @@ extern "C" int nbm_tiles_scatter_add(float* map, int B, int H, int W, int C, con
 }
 extern "C" int nbm_sqnorm_accum(const float* g, int64_t n, double* out, void* stream) {
   if (!g || !out || n <= 0) return NBM_EINVAL;
-  hipLaunchKernelGGL(sqnorm_kernel, dim3(grid_for(n, TPB, 2048)), dim3(TPB), 0, ST, g, (long long)n, out);
+  hipLaunchKernelGGL(sqnorm_kernel<false>, dim3(sqnorm_blocks(n)), dim3(TPB), 0, ST, g, (long long)n, out);
+  return nbm_launch_status();
+}
+extern "C" int nbm_sqnorm_accum_det(const float* g, int64_t n, double* out, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!g || !out || n <= 0) return NBM_EINVAL;
+  if (int rc = det_ws_check(workspace, workspace_bytes, det_bytes(NBM_DET_SQNORM, n, 1))) return rc;
+  const int blocks = sqnorm_blocks(n);
+  hipLaunchKernelGGL(sqnorm_kernel<true>, dim3(blocks), dim3(TPB), 0, ST, g, (long long)n, (double*)workspace);
+  nbm_ordered_sum_flat((const double*)workspace, blocks, 1, out, 1, ST);
   return nbm_launch_status();
 }
 extern "C" int nbm_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

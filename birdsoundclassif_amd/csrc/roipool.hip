@@ -147,6 +147,71 @@ __global__ __launch_bounds__(256) void roi_pool_hw_bwd_kernel(const RoiHwBwdPara
   }
 }
 
+// The deterministic twin (nbm_roi_pool_hw_bwd_det): the same sums in GATHER form.  A workgroup owns a 16 x 16 pixel tile of one level and
+// one image (blockIdx = tile, image; one launch per level).  It walks the image's RoIs in index order, 256 at a time: thread r works out
+// RoI r's window once (roi_window, the one statement of it) into LDS, then every (pixel, channel) work item of the tile adds, RoI by RoI
+// and bin by bin in ascending order, the shares of the bins that contain its pixel, and adds the total to the map once.  No atomic, one
+// fixed order per element.  A pixel outside every window is not written, so the kernel stays inside the footprint that
+// nbm_zero_roi_windows restores (the persistent demand-driven maps keep working), and a tile that no window touches costs its
+// workgroup the window pass only.  Cost: the window pass is B x tiles x n_roi roi_window calls, the gather loop visits n_roi LDS records
+// per work item -- linear in n_roi where the scatter form is constant; 16 RoIs per image in training, 1 000 at the evaluation geometry.
+struct RoiWin { int x1, y1, w, h; };      // w = 0: not on this level / no pixel in the map
+
+__global__ __launch_bounds__(256) void roi_pool_hw_bwd_gather_kernel(const RoiHwBwdParams p, int lvl) {
+  __shared__ RoiWin win[256];
+  __shared__ int any_s;
+  const int H = p.fh[lvl], W = p.fw[lvl], ph = p.ph, pw = p.pw, C = p.C, nbin = ph * pw;
+  const int tiles_x = (W + 15) >> 4;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x, b = blockIdx.y;
+  const int py0 = ty * 16, px0 = tx * 16;
+  const int th = min(16, H - py0), tw = min(16, W - px0);
+  float* gmap = p.gfmap[lvl] + (long long)b * H * W * C;
+  for (int r0 = 0; r0 < p.n_roi; r0 += 256) {
+    __syncthreads();                                    // the previous chunk's records are consumed
+    if (threadIdx.x == 0) any_s = 0;
+    __syncthreads();
+    const int r = r0 + threadIdx.x;
+    RoiWin wn = {0, 0, 0, 0};
+    if (r < p.n_roi) {
+      const long long slot = (long long)b * p.n_roi + r;
+      if (min(max(p.level[slot], 0), p.n_levels - 1) == lvl) {
+        int x1, y1, x2, y2;
+        if (roi_window(p.rois + slot * 4, lvl, H, W, ph, pw, x1, y1, x2, y2)) {
+          const int w = min(x2, W - 1) - x1 + 1, h = y2 - y1 + 1;
+          if (x1 < px0 + tw && x1 + w > px0 && y1 < py0 + th && y1 + h > py0) { wn = {x1, y1, w, h}; any_s = 1; }   // (benign: all store 1)
+        }
+      }
+    }
+    win[threadIdx.x] = wn;
+    __syncthreads();
+    if (!any_s) continue;                               // uniform
+    const int nr = min(256, p.n_roi - r0);
+    for (int it = threadIdx.x; it < th * tw * C; it += 256) {
+      const int c = it % C, px = it / C;
+      const int yy = py0 + px / tw, xx = px0 + px % tw;
+      float acc = 0.f;
+      bool hit = false;
+      for (int k = 0; k < nr; ++k) {
+        const RoiWin q = win[k];
+        const int dy = yy - q.y1, dx = xx - q.x1;
+        if (q.w == 0 || (unsigned)dy >= (unsigned)q.h || (unsigned)dx >= (unsigned)q.w) continue;
+        hit = true;
+        const float* g = p.gpool + ((long long)b * p.n_roi + r0 + k) * nbin * C + c;
+        for (int i = 0; i < ph; ++i) {
+          const int ya = (i * q.h) / ph, yb = ((i + 1) * q.h + ph - 1) / ph;
+          if (dy < ya || dy >= yb) continue;
+          for (int j = 0; j < pw; ++j) {
+            const int xa = (j * q.w) / pw, xb = ((j + 1) * q.w + pw - 1) / pw;
+            if (dx < xa || dx >= xb) continue;
+            acc += g[(long long)(i * pw + j) * C] / (float)((yb - ya) * (xb - xa));
+          }
+        }
+      }
+      if (hit) { float* o = gmap + ((long long)yy * W + xx) * C + c; *o = *o + acc; }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ demand-driven pyramid level: tiles under the RoIs
 // The finest FPN output map is read by two consumers only: the RPN's stride-8 depthwise convolution (a fixed pixel pattern)
 // and the RoI pooling of the RoIs assigned to that level.  This kernel lists the 2 x 2 Winograd output tiles of level `level`
@@ -157,8 +222,13 @@ __global__ __launch_bounds__(256) void roi_pool_hw_bwd_kernel(const RoiHwBwdPara
 struct RoiTilesParams {
   const float* rois; const int* n_roi; int B, roi_cap, n_levels, level, H, W;
   const unsigned char* skip; int* tiles; int* n_blocks; int dilate;
+  int* counts;           // deterministic twin: [B] blocks of every image (pass 1), placed by their exclusive prefix (pass 2); else null
 };
 
+// PASS 0: the default (blocks handed out by the atomic counter).  Deterministic twin: PASS 1 only counts (counts[b] = blocks of image b),
+// PASS 2 places image b's blocks at the exclusive prefix of counts -- the list is then ascending in (image, tile id) whatever the order the
+// workgroups run in -- and image 0's workgroup stores the total into *n_blocks.
+template <int PASS>
 __global__ __launch_bounds__(256) void roi_tiles_kernel(const RoiTilesParams p) {
   extern __shared__ unsigned bits[];
   __shared__ int part[256];
@@ -193,13 +263,20 @@ __global__ __launch_bounds__(256) void roi_tiles_kernel(const RoiTilesParams p) 
   if (tid == 0) {
     int run = 0;
     for (int i = 0; i < 256; ++i) { const int c = part[i]; part[i] = run; run += c; }
-    base_s = run ? atomicAdd(p.n_blocks, (run + 127) >> 7) : 0;
+    if (PASS == 0) base_s = run ? atomicAdd(p.n_blocks, (run + 127) >> 7) : 0;
+    else if (PASS == 1) p.counts[b] = (run + 127) >> 7;
+    else {
+      int before = 0, all = 0;
+      for (int i = 0; i < p.B; ++i) { if (i < b) before += p.counts[i]; all += p.counts[i]; }
+      base_s = before;
+      if (b == 0) *p.n_blocks = all;
+    }
     part[0] = 0;
     bits[n_words] = (unsigned)run;                               // total, one spare word
   }
   __syncthreads();
   const int total = (int)bits[n_words];
-  if (!total) return;
+  if (!total || PASS == 1) return;
   int* out = p.tiles + (long long)base_s * 128;
   int o = part[tid];
   for (int i = tid * wpt; i < min((tid + 1) * wpt, n_words); ++i) {
@@ -270,9 +347,9 @@ extern "C" int nbm_roi_pool_hw(const nbm_roi_hw_desc* d, void* stream) {
   return nbm_launch_status();
 }
 
-extern "C" int nbm_roi_pool_hw_bwd(float* const* gfmap, const int* fh, const int* fw, int n_levels, int C, const float* rois,
-                                   const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
-                                   void* stream) {
+static int roi_pool_hw_bwd_impl(float* const* gfmap, const int* fh, const int* fw, int n_levels, int C, const float* rois,
+                                const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
+                                int deterministic, void* stream) {
   if (!gfmap || !rois || !level || !gpool || B <= 0 || n_roi <= 0) return NBM_EINVAL;
   const int rc = roi_hw_check(n_levels, C, fh, fw, pool_h, pool_w);
   if (rc) return rc;
@@ -285,8 +362,25 @@ extern "C" int nbm_roi_pool_hw_bwd(float* const* gfmap, const int* fh, const int
   }
   p.n_levels = n_levels; p.C = C; p.rois = rois; p.level = level; p.B = B; p.n_roi = n_roi; p.gpool = gpool;
   p.ph = pool_h; p.pw = pool_w;
+  if (deterministic) {
+    if (B > 65535) return NBM_EUNSUPPORTED;
+    for (int l = 0; l < n_levels; ++l)
+      hipLaunchKernelGGL(roi_pool_hw_bwd_gather_kernel, dim3(((fh[l] + 15) / 16) * ((fw[l] + 15) / 16), B), dim3(256), 0,
+                         (hipStream_t)stream, p, l);
+    return nbm_launch_status();
+  }
   hipLaunchKernelGGL(roi_pool_hw_bwd_kernel, dim3(B * n_roi), dim3(256), 0, (hipStream_t)stream, p);
   return nbm_launch_status();
+}
+extern "C" int nbm_roi_pool_hw_bwd(float* const* gfmap, const int* fh, const int* fw, int n_levels, int C, const float* rois,
+                                   const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
+                                   void* stream) {
+  return roi_pool_hw_bwd_impl(gfmap, fh, fw, n_levels, C, rois, level, B, n_roi, pool_h, pool_w, gpool, 0, stream);
+}
+extern "C" int nbm_roi_pool_hw_bwd_det(float* const* gfmap, const int* fh, const int* fw, int n_levels, int C, const float* rois,
+                                       const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
+                                       void* stream) {
+  return roi_pool_hw_bwd_impl(gfmap, fh, fw, n_levels, C, rois, level, B, n_roi, pool_h, pool_w, gpool, 1, stream);
 }
 
 // The 2 x 2 entries of the ABI: the same checks and kernels with the pool size filled in.
@@ -306,9 +400,10 @@ extern "C" int nbm_roi_pool_bwd(float* const* gfmap, const int* fh, const int* f
 }
 
 // RoI windows of pyramid level `level` -> list of the 2 x 2 output tiles they touch -- see nbm_hip.h.
-extern "C" int nbm_roi_tiles(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level,
-                             const int* fh, const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks,
-                             void* stream) {
+// `counts` NULL: the default placement (atomic counter); else [B] ints of scratch for the deterministic placement
+static int roi_tiles_impl(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level,
+                          const int* fh, const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks,
+                          int* counts, void* stream) {
   if (!rois || !n_roi || !fh || !fw || !tiles || !n_blocks || B <= 0 || roi_cap <= 0 || n_levels < 1 || n_levels > 5 ||
       level < 0 || level >= n_levels || dilate < 0 || dilate > 2)
     return NBM_EINVAL;
@@ -322,10 +417,27 @@ extern "C" int nbm_roi_tiles(const float* rois, const int* n_roi, int B, int roi
   const size_t lds = (size_t)(((thw + 31) >> 5) + 1) * 4;
   if (lds > 60000) return NBM_EUNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  if (counts) {
+    p.counts = counts;
+    hipLaunchKernelGGL(roi_tiles_kernel<1>, dim3(B), dim3(256), lds, st, p);
+    hipLaunchKernelGGL(roi_tiles_kernel<2>, dim3(B), dim3(256), lds, st, p);
+    return nbm_launch_status();
+  }
   hipError_t e = nbm_zero_async(n_blocks, sizeof(int), st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(roi_tiles_kernel, dim3(B), dim3(256), lds, st, p);
+  hipLaunchKernelGGL(roi_tiles_kernel<0>, dim3(B), dim3(256), lds, st, p);
   return nbm_launch_status();
+}
+extern "C" int nbm_roi_tiles(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level,
+                             const int* fh, const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks,
+                             void* stream) {
+  return roi_tiles_impl(rois, n_roi, B, roi_cap, n_levels, level, fh, fw, skip, dilate, tiles, n_blocks, nullptr, stream);
+}
+extern "C" int nbm_roi_tiles_det(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level,
+                                 const int* fh, const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks,
+                                 int* counts, void* stream) {
+  if (!counts) return NBM_EINVAL;
+  return roi_tiles_impl(rois, n_roi, B, roi_cap, n_levels, level, fh, fw, skip, dilate, tiles, n_blocks, counts, stream);
 }
 
 extern "C" int nbm_zero_roi_windows(float* g, int H, int W, int C, const float* rois, const int* level, int B, int n_roi, int lvl,

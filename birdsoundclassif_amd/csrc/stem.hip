@@ -13,6 +13,7 @@
 // (r * pitch + s0) + 2 p + slot -- no im2col anywhere.  The folded weights [56][64] sit in LDS as the B operand.  bias_o(p)
 // is a per-channel constant for interior pixels and a masked 49-term sum on the three-pixel border.
 #include "nbm_common.h"
+#include "nbm_ordered_sum.h"
 
 namespace {
 
@@ -148,6 +149,9 @@ struct StemWgradParams {
   int B, H, W, Ho, Wo, n_strips, tiles_x;
 };
 
+// DET (both kernels, nbm_stem7x7_wgrad_det): the workgroup stores its accumulators into its own slot (D = part[gridDim.x][64][64],
+// Cb = part[gridDim.y * gridDim.x][64][49]) instead of the atomic flush; nbm_ordered_sum adds the slots in order.
+template <bool DET>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradParams p) {
   __shared__ __attribute__((aligned(16))) float img_s[7 * SP];
   __shared__ __attribute__((aligned(16))) float g_s[128 * 64];
@@ -211,7 +215,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradParams p
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int n = mt * 32 + (e & 3) + 8 * (e >> 2) + 4 * slot;
-    atomicAdd(p.D + n * 64 + col, acc[e]);
+    if (DET) p.D[(long long)blockIdx.x * 4096 + n * 64 + col] = acc[e];
+    else atomicAdd(p.D + n * 64 + col, acc[e]);
   }
 }
 
@@ -219,6 +224,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const StemWgradParams p
 // oy < top / oy >= bot0 and of the columns ox < left / ox >= right0 can have such taps: they are enumerated (all columns of the
 // border rows, then the border columns of the other rows); thread = (channel, one of 4 pixel streams), 49 running sums in
 // registers, one LDS reduction and 64 x 49 atomics per workgroup.
+template <bool DET>
 __global__ __launch_bounds__(256) void stem_vborder_kernel(const float* __restrict__ g, int H, int W, int Ho, int Wo, int top,
                                                            int bot0, int left, int right0, float* __restrict__ Cb) {
   __shared__ float red[4][64][49];
@@ -256,14 +262,25 @@ __global__ __launch_bounds__(256) void stem_vborder_kernel(const float* __restri
   for (int i = threadIdx.x; i < 64 * 49; i += 256) {
     const int nn = i / 49, e = i - nn * 49;
     const float v = red[0][nn][e] + red[1][nn][e] + red[2][nn][e] + red[3][nn][e];
-    if (v != 0.f) atomicAdd(Cb + i, v);
+    if (DET) Cb[((long long)blockIdx.y * gridDim.x + blockIdx.x) * (64 * 49) + i] = v;
+    else if (v != 0.f) atomicAdd(Cb + i, v);
   }
 }
 
 }  // namespace
 
-// U / S accumulators and the border correction of V -- see nbm_hip.h.
-extern "C" int nbm_stem7x7_wgrad(const float* img, const float* g, int B, int H, int W, float* D, float* Cb, void* stream) {
+static int stem_wgrad_grid(int B, int H, int W, long long* strips) {
+  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
+  *strips = (long long)B * Ho * ((Wo + 127) / 128);
+  return (int)(*strips < 1024 ? *strips : 1024);
+}
+static long long stem_wgrad_ws_floats(int B, int H, int W) {
+  long long strips;
+  return (long long)stem_wgrad_grid(B, H, W, &strips) * 4096 + 8ll * B * 64 * 49;
+}
+
+// U / S accumulators and the border correction of V -- see nbm_hip.h.  `workspace` NULL: the default kernels (atomic flush).
+static int stem7x7_wgrad_impl(const float* img, const float* g, int B, int H, int W, float* D, float* Cb, float* workspace, void* stream) {
   if (!img || !g || !D || !Cb || B <= 0 || H <= 0 || W <= 0) return NBM_EINVAL;
   if (!nbm_aligned16(g)) return NBM_EALIGN;
   StemWgradParams p{};
@@ -274,16 +291,43 @@ extern "C" int nbm_stem7x7_wgrad(const float* img, const float* g, int B, int H,
   if (strips > 0x7fffffffll) return NBM_EUNSUPPORTED;
   p.n_strips = (int)strips;
   hipStream_t st = (hipStream_t)stream;
+  if (workspace) {
+    const int grid = (int)(strips < 1024 ? strips : 1024);
+    float* cpart = workspace + (long long)grid * 4096;
+    p.D = workspace;
+    hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(grid), dim3(256), 0, st, p);
+    nbm_ordered_sum_flat((const float*)workspace, grid, 4096ll, D, 0, st);
+    int top = p.Ho < 2 ? p.Ho : 2, bot0 = top, left = p.Wo < 2 ? p.Wo : 2, right0 = left;
+    while (bot0 < p.Ho && 2 * bot0 + 3 < H) ++bot0;
+    while (right0 < p.Wo && 2 * right0 + 3 < W) ++right0;
+    hipLaunchKernelGGL(stem_vborder_kernel<true>, dim3(8, B), dim3(256), 0, st, g, H, W, p.Ho, p.Wo, top, bot0, left, right0, cpart);
+    nbm_ordered_sum_flat((const float*)cpart, 8 * B, 64ll * 49, Cb, 0, st);
+    return nbm_launch_status();
+  }
   if (nbm_zero_async(D, sizeof(float) * 64 * 64, st) != hipSuccess || nbm_zero_async(Cb, sizeof(float) * 64 * 49, st) != hipSuccess)
     return (int)hipGetLastError();
   const int grid = (int)(strips < 1024 ? strips : 1024);
-  hipLaunchKernelGGL(stem_wgrad_kernel, dim3(grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(grid), dim3(256), 0, st, p);
   // border rows / columns: taps reach outside for oy < 2 or 2 oy + 3 >= H (same for columns)
   int top = p.Ho < 2 ? p.Ho : 2, bot0 = top, left = p.Wo < 2 ? p.Wo : 2, right0 = left;
   while (bot0 < p.Ho && 2 * bot0 + 3 < H) ++bot0;
   while (right0 < p.Wo && 2 * right0 + 3 < W) ++right0;
-  hipLaunchKernelGGL(stem_vborder_kernel, dim3(8, B), dim3(256), 0, st, g, H, W, p.Ho, p.Wo, top, bot0, left, right0, Cb);
+  hipLaunchKernelGGL(stem_vborder_kernel<false>, dim3(8, B), dim3(256), 0, st, g, H, W, p.Ho, p.Wo, top, bot0, left, right0, Cb);
   return nbm_launch_status();
+}
+extern "C" int nbm_stem7x7_wgrad(const float* img, const float* g, int B, int H, int W, float* D, float* Cb, void* stream) {
+  return stem7x7_wgrad_impl(img, g, B, H, W, D, Cb, nullptr, stream);
+}
+extern "C" int nbm_stem7x7_wgrad_workspace(int B, int H, int W, int64_t* bytes) {
+  if (!bytes || B <= 0 || H <= 0 || W <= 0 || B > 65535) return NBM_EINVAL;
+  *bytes = stem_wgrad_ws_floats(B, H, W) * 4;
+  return NBM_OK;
+}
+extern "C" int nbm_stem7x7_wgrad_det(const float* img, const float* g, int B, int H, int W, float* D, float* Cb, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+  if (!workspace || B <= 0 || H <= 0 || W <= 0 || B > 65535 || workspace_bytes < stem_wgrad_ws_floats(B, H, W) * 4) return NBM_EINVAL;
+  if (!nbm_aligned16(workspace)) return NBM_EALIGN;
+  return stem7x7_wgrad_impl(img, g, B, H, W, D, Cb, (float*)workspace, stream);
 }
 
 // y = relu(bn(conv1(init_conv(img)))) -- see nbm_hip.h.

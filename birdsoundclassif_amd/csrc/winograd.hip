@@ -5,6 +5,7 @@
 // once per parameter version on the host.  All arithmetic fp32; fp32 error ~4x that of the direct kernel (3e-6 on O(1)
 // outputs), far inside the 1e-4 parity tolerance.
 #include "nbm_common.h"
+#include "nbm_ordered_sum.h"
 
 namespace {
 
@@ -133,6 +134,8 @@ __global__ __launch_bounds__(256) void wino23_output_kernel(const float* __restr
 // g [B][H][W][N] (gradient wrt the convolution output) -> dM [16][T][N] = (A g A^T) per 2x2 tile: the operand of the 16
 // weight-gradient GEMMs dU[xi] = dM[xi]^T V[xi].  Every thread also accumulates the plain sum of its pixels per channel
 // (bias gradient) over its grid-stride items -- its channel chunk is fixed because the stride is a multiple of N4.
+// DET (both output-gradient transforms): bias_grad is part[gridDim.x][N], see nbm_bias_slot_store.
+template <bool DET>
 __global__ __launch_bounds__(256) void wino23_outgrad_kernel(const float* __restrict__ g, int B, int H, int W, int N4,
                                                              float* __restrict__ dM, float* __restrict__ bias_grad,
                                                              const int* __restrict__ tiles, int n_list,
@@ -186,7 +189,9 @@ __global__ __launch_bounds__(256) void wino23_outgrad_kernel(const float* __rest
       m4[((long long)(a * 4 + 3) * T + t) * N4 + c] = -q;
     }
   }
-  if (bias_grad) {                     // uniform: per-thread sums -> LDS -> one global atomic per channel and workgroup
+  if (DET) {
+    if (bias_grad) { const float bs[4] = {bsum[0], bsum[1], bsum[2], bsum[3]}; nbm_bias_slot_store<4>(bs, N4, bias_grad); }
+  } else if (bias_grad) {              // uniform: per-thread sums -> LDS -> one global atomic per channel and workgroup
     __shared__ float red[WINO_MAX_BIAS_N];
     const int n = N4 * 4;
     for (int k = threadIdx.x; k < n; k += 256) red[k] = 0.f;
@@ -341,6 +346,7 @@ __global__ __launch_bounds__(256) void wino43_output_kernel(const float* __restr
 }
 
 // g [B][H][W][N] -> dM [36][T][N] = A g A^T per 4x4 tile (A = (A^T)^T, 6x4); bias gradient as in the F(2x2) kernel
+template <bool DET>
 __global__ __launch_bounds__(256) void wino43_outgrad_kernel(const float* __restrict__ g, int B, int H, int W, int N2,
                                                              float* __restrict__ dM, float* __restrict__ bias_grad) {
   const int TH = (H + 3) >> 2, TW = (W + 3) >> 2;
@@ -388,7 +394,9 @@ __global__ __launch_bounds__(256) void wino43_outgrad_kernel(const float* __rest
         m2[((long long)(k * 6 + j) * T + t) * N2 + c] = acc;
       }
   }
-  if (bias_grad) {                     // uniform: per-thread sums -> LDS -> one global atomic per channel and workgroup
+  if (DET) {
+    if (bias_grad) { const float bs[2] = {bsum[0], bsum[1]}; nbm_bias_slot_store<2>(bs, N2, bias_grad); }
+  } else if (bias_grad) {              // uniform: per-thread sums -> LDS -> one global atomic per channel and workgroup
     __shared__ float red[WINO_MAX_BIAS_N];
     const int n = N2 * 2;
     for (int k = threadIdx.x; k < n; k += 256) red[k] = 0.f;
@@ -511,7 +519,9 @@ extern "C" int nbm_wino_input(const float* x, int B, int H, int W, int C, float*
   return nbm_launch_status();
 }
 
-extern "C" int nbm_wino_outgrad(const float* g, int B, int H, int W, int N, float* dM, float* bias_grad, int m, void* stream) {
+// `workspace` NULL: the default bias flush (atomics); else the deterministic one (slots in `workspace`, added in order)
+static int wino_outgrad_impl(const float* g, int B, int H, int W, int N, float* dM, float* bias_grad, int m, float* workspace,
+                             long long workspace_bytes, void* stream) {
   if (!g || !dM || B <= 0 || H <= 0 || W <= 0 || N <= 0 || (N & 3) || (m != 2 && m != 4)) return NBM_EINVAL;
   if (!nbm_aligned16(g) || !nbm_aligned16(dM)) return NBM_EALIGN;
   if (bias_grad && N > WINO_MAX_BIAS_N) return NBM_EUNSUPPORTED;
@@ -522,12 +532,35 @@ extern "C" int nbm_wino_outgrad(const float* g, int B, int H, int W, int N, floa
   long long blocks = (total + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   while ((blocks * 256) % per) ++blocks;
+  if (workspace && bias_grad) {
+    if (!nbm_bias_slots_fit(workspace, workspace_bytes, blocks, N)) return NBM_EINVAL;
+    if (m == 2)
+      hipLaunchKernelGGL(wino23_outgrad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM, workspace,
+                         (const int*)nullptr, 0, (const unsigned*)nullptr, 0);
+    else
+      hipLaunchKernelGGL(wino43_outgrad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM, workspace);
+    nbm_ordered_sum_flat((const float*)workspace, (int)blocks, (long long)N, bias_grad, 1, (hipStream_t)stream);
+    return nbm_launch_status();
+  }
   if (m == 2)
-    hipLaunchKernelGGL(wino23_outgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM, bias_grad,
+    hipLaunchKernelGGL(wino23_outgrad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM, bias_grad,
                        (const int*)nullptr, 0, (const unsigned*)nullptr, 0);
   else
-    hipLaunchKernelGGL(wino43_outgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM, bias_grad);
+    hipLaunchKernelGGL(wino43_outgrad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM, bias_grad);
   return nbm_launch_status();
+}
+extern "C" int nbm_wino_outgrad(const float* g, int B, int H, int W, int N, float* dM, float* bias_grad, int m, void* stream) {
+  return wino_outgrad_impl(g, B, H, W, N, dM, bias_grad, m, nullptr, 0, stream);
+}
+extern "C" int nbm_wino_outgrad_det(const float* g, int B, int H, int W, int N, float* dM, float* bias_grad, int m, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  if (bias_grad && (!workspace || !nbm_aligned16(workspace))) return NBM_EINVAL;
+  return wino_outgrad_impl(g, B, H, W, N, dM, bias_grad, m, (float*)workspace, workspace_bytes, stream);
+}
+extern "C" int nbm_bias_grad_workspace(int N, int64_t* bytes) {
+  if (!bytes || N <= 0) return NBM_EINVAL;
+  *bytes = (int64_t)NBM_BIAS_SLOTS_MAX * N * 4;
+  return NBM_OK;
 }
 
 // F(2x2,3x3) input / output-gradient transforms of the listed tiles only (compact operands) -- see nbm_hip.h.
@@ -542,9 +575,9 @@ extern "C" int nbm_wino23_input_tiles(const float* x, int B, int H, int W, int C
   return nbm_launch_status();
 }
 
-extern "C" int nbm_wino23_outgrad_tiles(const float* g, int B, int H, int W, int N, const int* tiles, int n_list,
-                                        const unsigned* plane_mask, float* dM, float* bias_grad, int skip_pattern_stride,
-                                        void* stream) {
+static int wino23_outgrad_tiles_impl(const float* g, int B, int H, int W, int N, const int* tiles, int n_list,
+                                     const unsigned* plane_mask, float* dM, float* bias_grad, int skip_pattern_stride,
+                                     float* workspace, long long workspace_bytes, void* stream) {
   if (!g || !dM || !tiles || B <= 0 || H <= 0 || W <= 0 || N <= 0 || (N & 3) || n_list < 0 || skip_pattern_stride < 0) return NBM_EINVAL;
   if (!nbm_aligned16(g) || !nbm_aligned16(dM)) return NBM_EALIGN;
   if (n_list == 0) return NBM_OK;
@@ -554,9 +587,28 @@ extern "C" int nbm_wino23_outgrad_tiles(const float* g, int B, int H, int W, int
   long long blocks = ((long long)n_list * per + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   while ((blocks * 256) % per) ++blocks;              // a thread keeps one channel chunk (bias-gradient accumulation)
-  hipLaunchKernelGGL(wino23_outgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM,
+  if (workspace && bias_grad) {
+    if (!nbm_bias_slots_fit(workspace, workspace_bytes, blocks, N)) return NBM_EINVAL;
+    hipLaunchKernelGGL(wino23_outgrad_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM,
+                       workspace, tiles, n_list, plane_mask, skip_pattern_stride);
+    nbm_ordered_sum_flat((const float*)workspace, (int)blocks, (long long)N, bias_grad, 1, (hipStream_t)stream);
+    return nbm_launch_status();
+  }
+  hipLaunchKernelGGL(wino23_outgrad_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, B, H, W, per, dM,
                      bias_grad, tiles, n_list, plane_mask, skip_pattern_stride);
   return nbm_launch_status();
+}
+extern "C" int nbm_wino23_outgrad_tiles(const float* g, int B, int H, int W, int N, const int* tiles, int n_list,
+                                        const unsigned* plane_mask, float* dM, float* bias_grad, int skip_pattern_stride,
+                                        void* stream) {
+  return wino23_outgrad_tiles_impl(g, B, H, W, N, tiles, n_list, plane_mask, dM, bias_grad, skip_pattern_stride, nullptr, 0, stream);
+}
+extern "C" int nbm_wino23_outgrad_tiles_det(const float* g, int B, int H, int W, int N, const int* tiles, int n_list,
+                                            const unsigned* plane_mask, float* dM, float* bias_grad, int skip_pattern_stride,
+                                            void* workspace, int64_t workspace_bytes, void* stream) {
+  if (bias_grad && (!workspace || !nbm_aligned16(workspace))) return NBM_EINVAL;
+  return wino23_outgrad_tiles_impl(g, B, H, W, N, tiles, n_list, plane_mask, dM, bias_grad, skip_pattern_stride, (float*)workspace,
+                                   workspace_bytes, stream);
 }
 
 extern "C" int nbm_wino_output(const float* M, const float* scale, const float* shift, const float* mask, int relu, int B,

@@ -264,6 +264,21 @@ class LateralState:
         self.grads = None            # the lateral's own gradients, when the consumer's backward pass produced them (LAT_CELL_BWD)
 
 
+def set_deterministic_routes(flag, saved=None):
+    """The module switches deterministic mode sets (ops.set_deterministic) -> the values to hand back when it is switched off.
+    UPBWD_SPLIT off: the RoI share of the finest level's gradient then stays in the map and its bilinear backward runs through the dense
+    nbm_upsample_bilinear_bwd (gather form, no atomic) instead of the tile-wise scatter kernel, whose float atomics have no twin.  Every
+    other demand-driven route stays on: its kernels have twins and the tile lists are placed in (image, tile id) order."""
+    global UPBWD_SPLIT
+    if flag:
+        saved = {'UPBWD_SPLIT': UPBWD_SPLIT}
+        UPBWD_SPLIT = False
+        return saved
+    if saved:
+        UPBWD_SPLIT = saved['UPBWD_SPLIT']
+    return None
+
+
 ZERO_FILL = False                   # functional.py sets it when a DENSE backward kernel may read a sparse map (A/B switches off)
 
 
@@ -1008,8 +1023,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
             n_blocks = torch.zeros((1,), device=x.device, dtype=torch.int32)
         else:
             tiles, n_blocks = _roi_tile_buf(x.device, n_list)
-        check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, _ptr(st.skip), 0, _ptr(tiles),
-                                  _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
+        ops.roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, _ptr(st.skip), 0, _ptr(tiles), _ptr(n_blocks))
         if st.lateral is not None:                # the input patches of these tiles first (16 pixels per listed tile)
             lt = st.lateral
             gemm_conv(lt.t[b0:b0 + nb], lt.wk, x[b0:b0 + nb], B=nb, H=H, W=W, Cin=lt.t.shape[-1], N=C_, w_ld=lt.wk.shape[1],
@@ -1025,8 +1039,7 @@ def lazy_complete(fm, rois, n_roi, fmap_hw, level=0):
                 # the backward pass sizes the compact operands of the lateral's RoI share
                 tiles_d = torch.empty((n_list,), device=x.device, dtype=torch.int32)
                 nbd = torch.zeros((1,), device=x.device, dtype=torch.int32)
-                check(lib().nbm_roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, None, 1, _ptr(tiles_d), _ptr(nbd),
-                                          _stream()), 'nbm_roi_tiles')
+                ops.roi_tiles(_ptr(rois[b0:b0 + nb]), _ptr(nr), nb, cap, nl, level, fh, fw, None, 1, _ptr(tiles_d), _ptr(nbd))
                 host_d = _pinned_int()
                 host_d.copy_(nbd, non_blocking=True)
             ev = torch.cuda.Event()
@@ -1127,8 +1140,8 @@ def _cell_outgrad(st, g, ci, b0, nb):
     if st.cell_gb is None:
         st.cell_gb, st.cell_gb_done = torch.zeros((N,), device=g.device, dtype=torch.float32), set()
     vg = st.vg[ci] = torch.empty((25, T, N), device=g.device, dtype=torch.float32)
-    check(lib().nbm_cell_outgrad(_ptr(g[b0:b0 + nb]), nb, H, W, N, st.stride, _ptr(vg), None if ci in st.cell_gb_done else _ptr(st.cell_gb),
-                                 _stream()), 'nbm_cell_outgrad')
+    ops._reduction('nbm_cell_outgrad', (_ptr(g[b0:b0 + nb]), nb, H, W, N, st.stride, _ptr(vg),
+                                        None if ci in st.cell_gb_done else _ptr(st.cell_gb)), lambda: ops._bias_ws_bytes(N))
     st.cell_gb_done.add(ci)
     return vg
 
@@ -1234,14 +1247,14 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
             finally:
                 ops._PROFILE_LABEL = global_label
             if do_lat:            # d/d(merged map) patches (+ their sum = pattern share of the lateral's bias gradient), d/dt patches
-                check(lib().nbm_cell_dgrad_output(_ptr(M), nb, H, W, C_, st.stride, C.c_void_p(gx.data_ptr() + b0 * img_bytes), -1, K, 0,
-                                                  _ptr(gb_lat), _stream()), 'nbm_cell_dgrad_output')
-                check(lib().nbm_cell_dgrad_output(_ptr(M), nb, H, W, Cin, st.stride, C.c_void_p(dt.data_ptr() + b0 * dt_img_bytes), -1, K, C_,
-                                                  None, _stream()), 'nbm_cell_dgrad_output')
+                ops._reduction('nbm_cell_dgrad_output', (_ptr(M), nb, H, W, C_, st.stride, C.c_void_p(gx.data_ptr() + b0 * img_bytes), -1, K, 0,
+                                                         _ptr(gb_lat)), lambda: ops._bias_ws_bytes(C_))
+                ops._reduction('nbm_cell_dgrad_output', (_ptr(M), nb, H, W, Cin, st.stride, C.c_void_p(dt.data_ptr() + b0 * dt_img_bytes), -1, K,
+                                                         C_, None), lambda: ops._bias_ws_bytes(Cin))
             else:
                 for cls in (range(4) if overlap else (-1,)):
-                    check(lib().nbm_cell_dgrad_output(_ptr(M), nb, H, W, C_, st.stride, C.c_void_p(gx.data_ptr() + b0 * img_bytes), cls, mp, 0,
-                                                      None, _stream()), 'nbm_cell_dgrad_output')
+                    ops._reduction('nbm_cell_dgrad_output', (_ptr(M), nb, H, W, C_, st.stride, C.c_void_p(gx.data_ptr() + b0 * img_bytes), cls, mp,
+                                                             0, None), lambda: ops._bias_ws_bytes(C_))
         else:
             pat = wino23_pattern(nb, H, W, st.stride, g.device, dilate=1)
             _wino23_tiles_run(g[b0:b0 + nb], Ut, None, gx.data_ptr() + b0 * img_bytes, pat.tiles, None, pat.n_eff, 'wino23-dgrad',
@@ -1278,9 +1291,9 @@ def conv3x3_winograd_dgrad_tiles(st, g, Ut, Ucell=None, base=None, lateral_grads
                             _note_zero_tiles(pl, p_, nb, H, W, c_, tl, n, None)
                 continue
             tiles, n_blocks = _roi_tile_buf(g.device, nb * blocks_per_img * 128)
-            check(lib().nbm_roi_tiles(_ptr(pooling.rois[b0:b0 + nb]), _ptr(pooling.n_roi[b0:b0 + nb]), nb, pooling.rois.shape[1],
-                                      pooling.n_levels, pooling.level, pooling.fh, pooling.fw, None if cell else _ptr(pat.full), 1,
-                                      _ptr(tiles), _ptr(n_blocks), _stream()), 'nbm_roi_tiles')
+            ops.roi_tiles(_ptr(pooling.rois[b0:b0 + nb]), _ptr(pooling.n_roi[b0:b0 + nb]), nb, pooling.rois.shape[1],
+                          pooling.n_levels, pooling.level, pooling.fh, pooling.fw, None if cell else _ptr(pat.full), 1,
+                          _ptr(tiles), _ptr(n_blocks))
             # composed reader: g holds the RoI pooling's share only (pattern pixels included), ADDED to the cell patches
             _wino23_tiles_run(g[b0:b0 + nb], Ut, None, gx.data_ptr() + b0 * img_bytes, tiles, n_blocks, None, 'wino23-dgrad-rois',
                               skip_pattern=st.stride if (overlap and comp is None) else 0, accumulate=overlap or comp is not None)
@@ -1388,8 +1401,8 @@ def conv3x3_winograd_wgrad_tiles(st, x, g, want_bias=False, cell=None):
             V, dM = ops._wino_scratch(x.device, 16 * L * C_, 16 * L * N)
             check(lib().nbm_wino23_input_tiles(_ptr(xs), nb, H, W, C_, _ptr(lst), L, _ptr(info[l0:]), _ptr(V), stream),
                   'nbm_wino23_input_tiles')
-            check(lib().nbm_wino23_outgrad_tiles(_ptr(gs), nb, H, W, N, _ptr(lst), L, _ptr(info[l0:]), _ptr(dM), _ptr(gb),
-                                                 st.stride if (cell and comp is None) else 0, stream), 'nbm_wino23_outgrad_tiles')
+            ops._reduction('nbm_wino23_outgrad_tiles', (_ptr(gs), nb, H, W, N, _ptr(lst), L, _ptr(info[l0:]), _ptr(dM), _ptr(gb),
+                                                        st.stride if (cell and comp is None) else 0), lambda: ops._bias_ws_bytes(N))
             conv_wgrad(dM, V, dU, B=1, H=L, W=1, Cin=C_, N=N, groups=16, g_gs=L * N, x_gs=L * C_, out_gs=N * C_)
     if cell and gb is not None:
         share = comp['gb'] if comp is not None else st.cell_gb

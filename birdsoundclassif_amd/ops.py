@@ -73,6 +73,145 @@ def lib():
     return _lib.load()
 
 
+# --------------------------------------------------------------------------- deterministic mode
+# Entry points whose DEFAULT kernels sum with floating-point atomics, and the twin that replaces each of them while the mode is on.
+# 'desc': the twin is selected inside the same entry point by descriptor fields (nbm_bwd_desc.workspace); None: no twin -- a call in
+# deterministic mode raises.  Every call of these entry points goes through `_reduction`, so the table is the one place a new atomic
+# kernel has to be entered (tests/test_deterministic_cpu.py checks the sources against tests/golden/atomic_sites.json).
+ATOMIC_ENTRY_POINTS = {
+    'nbm_conv_wgrad': 'desc',
+    'nbm_stem7x7_wgrad': 'nbm_stem7x7_wgrad_det',
+    'nbm_wino_outgrad': 'nbm_wino_outgrad_det',
+    'nbm_wino23_outgrad_tiles': 'nbm_wino23_outgrad_tiles_det',
+    'nbm_cell_outgrad': 'nbm_cell_outgrad_det',
+    'nbm_cell_dgrad_output': 'nbm_cell_dgrad_output_det',
+    'nbm_roi_pool_hw_bwd': 'nbm_roi_pool_hw_bwd_det',
+    'nbm_roi_pool_bwd': None,                   # (the 2 x 2 alias; the op layer only calls nbm_roi_pool_hw_bwd)
+    'nbm_roi_tiles': 'nbm_roi_tiles_det',
+    'nbm_colsum': 'nbm_colsum_det',
+    'nbm_weighted_sum_bwd': 'nbm_weighted_sum_bwd_det',
+    'nbm_dwconv3x3_bwd': 'nbm_dwconv3x3_bwd_det',
+    'nbm_bn_train_fwd': 'nbm_bn_train_fwd_det',
+    'nbm_bn_train_bwd': 'nbm_bn_train_bwd_det',
+    'nbm_sqnorm_accum': 'nbm_sqnorm_accum_det',
+    'nbm_layernorm_bwd': 'nbm_layernorm_bwd_det',          # (an entry point of its own since the dropout path: `layernorm_bwd` routes)
+    'nbm_tiles_upsample_bilinear_bwd_add': None,           # deterministic mode routes through the dense nbm_upsample_bilinear_bwd
+}
+DET_COLSUM, DET_SQNORM, DET_BN, DET_WEIGHTED_SUM, DET_DWCONV = range(5)      # nbm_det_workspace's `op`
+
+_DET = {'on': False, 'torch': None, 'saved': None, 'ws': {}}
+
+
+def deterministic():
+    """Is the process in deterministic mode (`set_deterministic`)?"""
+    return _DET['on']
+
+
+def _det_refusals():
+    """Options whose kernels have no deterministic twin: -> [(option, why)]."""
+    bad = []
+    if os.environ.get('NBM_SPLIT_BF16') == '1':
+        bad.append(('NBM_SPLIT_BF16=1', 'the split-bf16 weight-gradient kernel (igemm_split_tn.hip) adds its pixel splits with atomics'))
+    return bad
+
+
+class _DetScope:
+    """What `set_deterministic` returns: usable as a context manager that restores the previous state on exit."""
+
+    def __init__(self, previous):
+        self.previous = previous
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.previous)
+
+
+def set_deterministic(flag):
+    """Switch the process-wide deterministic mode (train.py --deterministic).  On: every entry point of ATOMIC_ENTRY_POINTS runs
+    its twin (no atomics, fixed summation order), the demand-driven routes whose kernels have none are routed densely
+    (`ondemand.set_deterministic_routes`) and torch.use_deterministic_algorithms(True) holds; off: all of that is restored.  An option
+    that is not covered is refused by name (ValueError).  -> a context manager restoring the previous state (`with
+    set_deterministic(True): ...`); calling it plainly just switches."""
+    flag = bool(flag)
+    previous = _DET['on']
+    if flag == previous:
+        return _DetScope(previous)
+    from . import ondemand
+    if flag:
+        bad = _det_refusals()
+        if bad:
+            raise ValueError('--deterministic does not cover ' + '; '.join(f'{o} ({why})' for o, why in bad))
+        _DET['torch'] = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
+        torch.use_deterministic_algorithms(True)
+        _DET['saved'] = ondemand.set_deterministic_routes(True)
+        _DET['on'] = True
+    else:
+        _DET['on'] = False
+        ondemand.set_deterministic_routes(False, _DET['saved'])
+        torch.use_deterministic_algorithms(_DET['torch'][0], warn_only=_DET['torch'][1])
+        _DET['torch'] = _DET['saved'] = None
+        _DET['ws'].clear()
+    return _DetScope(previous)
+
+
+def _det_workspace(nbytes, device=None):
+    """The twins' slot workspace: one growing buffer per stream (launches on a stream are ordered, so consecutive twins share it); never
+    zeroed, its contents are never read before they are written."""
+    key = torch.cuda.current_stream().cuda_stream
+    buf = _DET['ws'].get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = None
+        _DET['ws'][key] = None
+        buf = torch.empty((max(int(nbytes), 1 << 20),), device=device or 'cuda', dtype=torch.uint8)
+        _DET['ws'][key] = buf
+    return buf
+
+
+def det_workspace_bytes():
+    """Bytes currently held by the deterministic twins' workspaces (all streams)."""
+    return sum(b.numel() for b in _DET['ws'].values() if b is not None)
+
+
+def _det_bytes(op, rows, cols=1):
+    n = C.c_int64(0)
+    check(lib().nbm_det_workspace(int(op), int(rows), int(cols), C.byref(n)), 'nbm_det_workspace')
+    return n.value
+
+
+def _bias_ws_bytes(N):
+    n = C.c_int64(0)
+    check(lib().nbm_bias_grad_workspace(int(N), C.byref(n)), 'nbm_bias_grad_workspace')
+    return n.value
+
+
+def roi_tiles(*args):
+    """nbm_roi_tiles on the current stream (args: everything but the stream; args[2] is the image count) -- in deterministic mode its
+    twin, which places the 128-entry blocks by a prefix over the images instead of an atomic counter."""
+    if not _DET['on']:
+        return check(lib().nbm_roi_tiles(*args, _stream()), 'nbm_roi_tiles')
+    counts = _det_workspace(4 * int(args[2]))
+    return check(lib().nbm_roi_tiles_det(*args, _ptr(counts), _stream()), 'nbm_roi_tiles_det')
+
+
+def _reduction(name, args, ws_bytes=None):
+    """Call entry point `name` of ATOMIC_ENTRY_POINTS with `args` (everything but the stream) on the current stream -- in deterministic
+    mode its twin, with `ws_bytes()` bytes of slot workspace appended where the twin takes one (ws_bytes None: it takes none)."""
+    twin = ATOMIC_ENTRY_POINTS[name]
+    if not _DET['on']:
+        return check(getattr(lib(), name)(*args, _stream()), name)
+    if twin == 'desc':
+        raise TypeError(f'{name} selects its twin through descriptor fields: call it through its op-layer wrapper')
+    if twin is None:
+        raise RuntimeError(f'{name} is not reproducible under --deterministic')
+    if ws_bytes is None:
+        return check(getattr(lib(), twin)(*args, _stream()), twin)
+    nbytes = int(ws_bytes())
+    ws = _det_workspace(nbytes)
+    return check(getattr(lib(), twin)(*args, _ptr(ws), nbytes, _stream()), twin)
+
+
 # --------------------------------------------------------------------------- implicit GEMM
 def gemm_conv(x, w, y, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, Ho=None, Wo=None,
               x_ld=None, w_ld=None, y_ld=None, scale=None, shift=None, residual=None, res_ld=None,
@@ -412,7 +551,7 @@ def conv3x3_winograd_wgrad(x, g, want_bias=False, m=2):
         nb = min(chunk, B - b0)
         T = nb * tiles
         check(lib().nbm_wino_input(_ptr(x[b0:b0 + nb]), nb, H, W, C_, _ptr(V), m, st), 'nbm_wino_input')
-        check(lib().nbm_wino_outgrad(_ptr(g[b0:b0 + nb]), nb, H, W, N, _ptr(dM), _ptr(gb), m, st), 'nbm_wino_outgrad')
+        _reduction('nbm_wino_outgrad', (_ptr(g[b0:b0 + nb]), nb, H, W, N, _ptr(dM), _ptr(gb), m), lambda: _bias_ws_bytes(N))
         conv_wgrad(dM, V, dU, B=1, H=T, W=1, Cin=C_, N=N, groups=nxi, g_gs=T * N, x_gs=T * C_, out_gs=N * C_)
     return dU, gb
 
@@ -674,7 +813,11 @@ def stem7x7_wgrad(img, g):
     assert g.shape == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64)
     D = torch.empty((64, 64), device=img.device, dtype=torch.float32)
     Cb = torch.empty((64, 49), device=img.device, dtype=torch.float32)
-    check(lib().nbm_stem7x7_wgrad(_ptr(img), _ptr(g), B, H, W, _ptr(D), _ptr(Cb), _stream()), 'nbm_stem7x7_wgrad')
+    def ws_bytes():
+        n = C.c_int64(0)
+        check(lib().nbm_stem7x7_wgrad_workspace(B, H, W, C.byref(n)), 'nbm_stem7x7_wgrad_workspace')
+        return n.value
+    _reduction('nbm_stem7x7_wgrad', (_ptr(img), _ptr(g), B, H, W, _ptr(D), _ptr(Cb)), ws_bytes)
     U = D[:, :56].view(64, 7, 8)[:, :, :7]
     V = D[:, 56].view(64, 1, 1) - Cb.view(64, 7, 7)
     return U, V
@@ -1439,6 +1582,16 @@ def conv_wgrad(g, x, out, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, g_ld=
         if gemm_plan(2, d).kernel.startswith('igemm_split_tn_kernel'):
             deferred_bias, bias_grad = bias_grad, None
     d.bias_grad = bias_grad.data_ptr() if bias_grad is not None else None       # [N] zeros: += column sums of g
+    if deterministic():
+        bad = _det_refusals()              # (an option switched on after the mode was: refused here, not run on its atomics)
+        if bad:
+            raise ValueError('--deterministic does not cover ' + '; '.join(f'{o} ({why})' for o, why in bad))
+        # the twin: every pixel split stores its slice of the workspace, an ordered reduction adds them (nbm_bwd_desc.workspace).
+        # (A slice beyond the workspace ceiling is refused by the query: NBM_EUNSUPPORTED.)
+        nbytes, stride = wgrad_workspace(d)
+        if nbytes:
+            ws = _det_workspace(nbytes)
+            d.workspace, d.ws_split_stride, d.workspace_bytes = ws.data_ptr(), stride, nbytes
     if FLOPS is not None:
         FLOPS[0] += 2.0 * B * d.Ho * d.Wo * N * kh * kw * Cin * groups
     with _timed(('wgrad', B, H, W, Cin, N, kh, stride, groups)):
@@ -1447,6 +1600,14 @@ def conv_wgrad(g, x, out, *, B, H, W, Cin, N, kh=1, kw=1, stride=1, pad=0, g_ld=
         gl = N if g_ld is None else g_ld
         deferred_bias += colsum(g.reshape(-1)[:B * H * W * gl].view(B * H * W, gl), N)
     return out
+
+
+def wgrad_workspace(desc):
+    """(bytes, floats between the slices of consecutive splits) of the deterministic twin of nbm_conv_wgrad for a BwdDesc
+    (nbm_conv_wgrad_workspace: host only, works without a GPU); bytes = 0: one split and no bias gradient, nothing to order."""
+    nbytes, stride = C.c_int64(0), C.c_int64(0)
+    check(lib().nbm_conv_wgrad_workspace(C.byref(desc), C.byref(nbytes), C.byref(stride)), 'nbm_conv_wgrad_workspace')
+    return nbytes.value, stride.value
 
 
 def _gconv_bwd_desc(B, H, W, groups, Cg, stride, kh=3, kw=3, pad=1, splits=0):
@@ -1605,6 +1766,8 @@ def leaky_relu_bwd(gy, y, slope=0.01):
 
 def layernorm_bwd(x2d, w, g2d, eps=1e-5):
     """-> (gx [rows,E], gw [E], gb [E])."""
+    if deterministic():
+        return layernorm_bwd_det(x2d, w, g2d, eps)
     rows, E = x2d.shape
     gx = torch.empty_like(x2d)
     gwb = torch.zeros((2, E), device=x2d.device, dtype=torch.float32)
@@ -1658,9 +1821,9 @@ def weighted_sum_bwd(xs, weights, g, need):
     x2 = xs[2] if len(xs) == 3 else None
     gxs = [torch.empty_like(x) if nd else None for x, nd in zip(xs, need)] + [None] * (3 - len(xs))
     gw = torch.zeros((len(xs),), device=g.device, dtype=torch.float32)
-    check(lib().nbm_weighted_sum_bwd(_ptr(_chk(xs[0])), _ptr(_chk(xs[1])), _ptr(x2), _ptr(_chk(weights)), _ptr(_chk(g)),
-                                     _ptr(gxs[0]), _ptr(gxs[1]), _ptr(gxs[2]), _ptr(gw), g.numel(), _stream()),
-          'nbm_weighted_sum_bwd')
+    _reduction('nbm_weighted_sum_bwd', (_ptr(_chk(xs[0])), _ptr(_chk(xs[1])), _ptr(x2), _ptr(_chk(weights)), _ptr(_chk(g)),
+                                        _ptr(gxs[0]), _ptr(gxs[1]), _ptr(gxs[2]), _ptr(gw), g.numel()),
+               lambda: _det_bytes(DET_WEIGHTED_SUM, g.numel()))
     return gxs[:len(xs)], gw
 
 
@@ -1670,7 +1833,7 @@ def colsum(g2d, n=None):
     M, ld = g2d.shape
     n = ld if n is None else n
     out = torch.empty((n,), device=g2d.device, dtype=torch.float32)
-    check(lib().nbm_colsum(_ptr(g2d), M, n, ld, _ptr(out), _stream()), 'nbm_colsum')
+    _reduction('nbm_colsum', (_ptr(g2d), M, n, ld, _ptr(out)), lambda: _det_bytes(DET_COLSUM, M, n))
     return out
 
 
@@ -1693,6 +1856,8 @@ def upsample_bilinear_bwd(gy, Hi, Wi, pattern_stride=0, tiles_share=()):
     gs = torch.empty((B, Hi, Wi, C_), device=gy.device, dtype=torch.float32)
     check(lib().nbm_upsample_bilinear_bwd(_ptr(_chk(gy)), B, Hi, Wi, C_, _ptr(gs), Ho, Wo, int(pattern_stride), _stream()),
           'nbm_upsample_bilinear_bwd')
+    if tiles_share and deterministic():       # (ondemand.UPBWD_SPLIT is off in deterministic mode: nothing should get here)
+        raise RuntimeError('nbm_tiles_upsample_bilinear_bwd_add is not reproducible under --deterministic')
     for compact, tiles, b0, nb in tiles_share:
         if compact.shape != (tiles.numel() * 4, C_) or b0 < 0 or b0 + nb > B:
             raise ValueError('upsample_bilinear_bwd: compact operand / tile list / image range do not fit the map')
@@ -1723,8 +1888,8 @@ def dwconv3x3_bwd(x, g, w, mult, stride, need_gx=True, need_gw=True, has_bias=Tr
     gx = torch.empty_like(x) if need_gx else None
     gw = torch.empty((Cin * mult, 1, 3, 3), device=x.device, dtype=torch.float32) if need_gw else None
     gb = torch.empty((Cin * mult,), device=x.device, dtype=torch.float32) if (need_gw and has_bias) else None
-    check(lib().nbm_dwconv3x3_bwd(_ptr(_chk(x)), _ptr(_chk(g)), _ptr(_chk(w)), B, H, W, Cin, mult, stride, _ptr(gx),
-                                  _ptr(gw), _ptr(gb), Ho, Wo, _stream()), 'nbm_dwconv3x3_bwd')
+    _reduction('nbm_dwconv3x3_bwd', (_ptr(_chk(x)), _ptr(_chk(g)), _ptr(_chk(w)), B, H, W, Cin, mult, stride, _ptr(gx),
+                                     _ptr(gw), _ptr(gb), Ho, Wo), lambda: _det_bytes(DET_DWCONV, B * Ho * Wo, Cin * mult))
     return gx, gw, gb
 
 
@@ -1757,9 +1922,9 @@ def bn_train_fwd(x2d, w, b, eps, momentum, run_mean, run_var):
     mean = torch.empty((C_,), device=x2d.device, dtype=torch.float32)
     invstd = torch.empty_like(mean)
     y = torch.empty_like(x2d)
-    check(lib().nbm_bn_train_fwd(_ptr(_chk(x2d)), M, C_, _ptr(_chk(w)), _ptr(_chk(b)), float(eps), float(momentum),
-                                 _ptr(run_mean), _ptr(run_var), _ptr(ws), _ptr(mean), _ptr(invstd), _ptr(y), _stream()),
-          'nbm_bn_train_fwd')
+    _reduction('nbm_bn_train_fwd', (_ptr(_chk(x2d)), M, C_, _ptr(_chk(w)), _ptr(_chk(b)), float(eps), float(momentum),
+                                    _ptr(run_mean), _ptr(run_var), _ptr(ws), _ptr(mean), _ptr(invstd), _ptr(y)),
+               lambda: _det_bytes(DET_BN, M, C_))
     return y, mean, invstd
 
 
@@ -1769,8 +1934,8 @@ def bn_train_bwd(g2d, x2d, mean, invstd, w):
     gx = torch.empty_like(x2d)
     gw = torch.empty((C_,), device=x2d.device, dtype=torch.float32)
     gb = torch.empty_like(gw)
-    check(lib().nbm_bn_train_bwd(_ptr(_chk(g2d)), _ptr(_chk(x2d)), M, C_, _ptr(mean), _ptr(invstd), _ptr(_chk(w)), _ptr(ws),
-                                 _ptr(gx), _ptr(gw), _ptr(gb), _stream()), 'nbm_bn_train_bwd')
+    _reduction('nbm_bn_train_bwd', (_ptr(_chk(g2d)), _ptr(_chk(x2d)), M, C_, _ptr(mean), _ptr(invstd), _ptr(_chk(w)), _ptr(ws),
+                                    _ptr(gx), _ptr(gw), _ptr(gb)), lambda: _det_bytes(DET_BN, M, C_))
     return gx, gw, gb
 
 
@@ -1875,8 +2040,7 @@ def roi_pool_bwd(gpool, rois, level, fmap_shapes, pooled=None, bases=None):
     ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in gf])
     fh = (C.c_int * n)(*[s[1] for s in fmap_shapes])
     fw = (C.c_int * n)(*[s[2] for s in fmap_shapes])
-    check(lib().nbm_roi_pool_hw_bwd(ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, ph, pw, _ptr(_chk(gpool)),
-                                    _stream()), 'nbm_roi_pool_hw_bwd')
+    _reduction('nbm_roi_pool_hw_bwd', (ptrs, fh, fw, n, C_, _ptr(_chk(rois)), _ptr(level), B, R, ph, pw, _ptr(_chk(gpool))))
     return gf
 
 
@@ -1892,7 +2056,7 @@ def _check_all_zero(buf):
 
 
 def sqnorm_accum(g, out):
-    check(lib().nbm_sqnorm_accum(_ptr(g), g.numel(), _ptr(out), _stream()), 'nbm_sqnorm_accum')
+    _reduction('nbm_sqnorm_accum', (_ptr(g), g.numel(), _ptr(out)), lambda: _det_bytes(DET_SQNORM, g.numel()))
 
 
 def adamw_step(p, g, m, v, lr, beta1, beta2, eps, wd, step, sqnorm=None, max_norm=0.0):

@@ -49,7 +49,14 @@ def get_args_parser():
     a('--validation_prop', default=0.03, type=float)
     # not a reference flag: workers ship the PNG files' zlib streams and the GPU inflates them (nbm_png_inflate)
     a('--device_inflate', action='store_true', default=False)
+    # not a reference flag: reproducible training -- every reduction of the step on its deterministic twin (ops.set_deterministic)
+    a('--deterministic', action='store_true', default=False)
     return p
+
+
+def wants_deterministic(args):
+    """--deterministic of an args namespace; an `args` file written before the flag existed has no such key and means off."""
+    return bool(getattr(args, 'deterministic', False))
 
 
 def default_args(device='cuda', **overrides):
@@ -132,6 +139,21 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _mark(self, p):
         self._touched.add(id(p))
+
+    def release(self):
+        """Give the device memory back and let go of the parameters: the flat buffers, the optimiser state and the entries in
+        `functional.GRAD_SINK` (which keep a finished optimiser reachable until another parameter lands on the same address).  The
+        parameters keep their shapes' names but hold empty storages afterwards: for a model and optimiser that are done (a test, a
+        sweep over configurations in one process).  The optimiser cannot step after this."""
+        from .nets import functional as Fn
+        for key in [k for k, (_, mark) in Fn.GRAD_SINK.items() if getattr(mark, '__self__', None) is self]:
+            del Fn.GRAD_SINK[key]
+        for p in self.all_params():
+            p.grad = None
+            p.data = torch.empty(0, device=p.device, dtype=p.dtype)
+        self._flat.clear()
+        self.state.clear()
+        self._touched.clear()
 
     def all_params(self):
         """Every parameter in flat-buffer order (the order of the `touched` bitmap exchanged between ranks)."""
@@ -666,6 +688,8 @@ def main(args):
     setattr_others(args)
     val_freq, log_freq = getattr(args, 'val_freq', 500), getattr(args, 'log_freq', 50)
 
+    from . import ops
+    ops.set_deterministic(wants_deterministic(args))     # before the model is built: an option it does not cover is refused here
     model, criterion = build_model(args)
     model.to(device)
     optimizer, lr_scheduler = build_optimizer(model, args)

@@ -201,6 +201,13 @@ int nbm_wino_output(const float* M, const float* scale, const float* shift, cons
 /* weight gradient side: dM[xi][t][n] = (A g A^T)[xi] of the m x m output-gradient tile; dU[xi] = dM[xi]^T V[xi] through
  * nbm_conv_wgrad (groups = (m+2)^2) and dW = G^T dU G on the host.  bias_grad [N] (may be NULL): += sum over pixels of g. */
 int nbm_wino_outgrad(const float* g, int B, int H, int W, int N, float* dM, float* bias_grad, int m, void* stream);
+/* Deterministic twins of the four transforms whose bias gradient rides along (nbm_wino_outgrad, nbm_wino23_outgrad_tiles,
+ * nbm_cell_outgrad, nbm_cell_dgrad_output): instead of LDS atomics followed by global ones, every workgroup adds its threads' shares in
+ * thread order and stores them into its own slot of `workspace` (16-byte aligned, >= nbm_bias_grad_workspace(N) bytes, never zeroed); an
+ * ordered reduction adds the slots into bias_grad (still +=).  Everything else is the default kernel.  nbm_bias_grad_workspace: host only. */
+int nbm_bias_grad_workspace(int N, int64_t* bytes);
+int nbm_wino_outgrad_det(const float* g, int B, int H, int W, int N, float* dM, float* bias_grad, int m, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 
 /* Weight side of the Winograd convolutions (csrc/winograd.hip).
  *   nbm_wino_weight:      g [N][C][3][3] (checkpoint layout) -> U [(m+2)^2][N'][C'] = G g' G^T in float64, rounded once.
@@ -254,6 +261,11 @@ int nbm_wino23_conv_fused_tiles(const float* R, const float* U, const float* sca
                                 const int* n_blocks, const unsigned* blk_info, void* stream);
 int nbm_roi_tiles(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level, const int* fh,
                   const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks, void* stream);
+/* Deterministic twin: the blocks are placed by the exclusive prefix of the images' block counts (a counting pass into `counts`, [B] ints of
+ * device scratch, then the placing pass) instead of an atomic counter, so the list is ascending in (image, tile id) on every launch and
+ * every kernel that sums over the list sums in that order. */
+int nbm_roi_tiles_det(const float* rois, const int* n_roi, int B, int roi_cap, int n_levels, int level, const int* fh,
+                      const int* fw, const unsigned char* skip, int dilate, int* tiles, int* n_blocks, int* counts, void* stream);
 /* Weight gradient of such a demand-driven convolution: the gradient wrt its output is zero outside the tiles that were
  * read, so only those tiles enter dU[xi] = dM[xi]^T V[xi].  F(2x2,3x3) transforms of the listed tiles (entry -1 = a zero
  * row) into COMPACT operands V [16][n_list][C] and dM [16][n_list][N] (+ bias gradient [N], optional, accumulated); the 16
@@ -266,6 +278,9 @@ int nbm_wino23_input_tiles(const float* x, int B, int H, int W, int C, const int
                            float* V, void* stream);
 int nbm_wino23_outgrad_tiles(const float* g, int B, int H, int W, int N, const int* tiles, int n_list, const unsigned* plane_mask,
                              float* dM, float* bias_grad, int skip_pattern_stride, void* stream);
+int nbm_wino23_outgrad_tiles_det(const float* g, int B, int H, int W, int N, const int* tiles, int n_list, const unsigned* plane_mask,
+                                 float* dM, float* bias_grad, int skip_pattern_stride, void* workspace, int64_t workspace_bytes,
+                                 void* stream);
 /* Backward pass of the same convolution over the PATTERN pixels of its output gradient (what autograd derives for
  * fpn.py:145 from the RPN's stride-S depthwise convolution, layers.py:62-65,81): the gradient is one 3x3 block per S x S cell
  * (rows S*oy-1 .. S*oy+1, cells = output pixels of the 3x3 / stride-S / pad-1 reader), so per cell the data gradient is the
@@ -280,6 +295,8 @@ int nbm_wino23_outgrad_tiles(const float* g, int B, int H, int W, int N, const i
  *                          overlapping patches of a stride-3 / 4 pattern)
  * the weight gradient's 25 TN GEMMs dU_xi = Vg_xi^T Vx_xi are nbm_conv_wgrad with groups = 25; dW = E^T dU E on the host. */
 int nbm_cell_outgrad(const float* g, int B, int H, int W, int N, int stride, float* Vg, float* bias_grad, void* stream);
+int nbm_cell_outgrad_det(const float* g, int B, int H, int W, int N, int stride, float* Vg, float* bias_grad, void* workspace,
+                         int64_t workspace_bytes, void* stream);
 /* Kernel side of the same algorithm (float64 arithmetic on the device, one rounding; replaces the reference-side autograd of
  * fpn.py:137,145's weights through torch.einsum):
  *   nbm_cell_weight       w [N][C][3][3] (checkpoint layout) -> U = E w E^T as U_nc [25][N][ld] (columns 0..C-1: B operand of the
@@ -323,6 +340,8 @@ int nbm_copy_rect(float* strided, float* packed, int64_t n_outer, int64_t outer_
 int nbm_cell_dgrad_output(const float* M, int B, int H, int W, int C, int stride, float* gx, int parity_class,
                           int ld /* row pitch of M, >= c_off + C */, int c_off /* first channel of M read */,
                           float* bias_grad /* optional [C]: += sum of the patch pixels written (inside the image) */, void* stream);
+int nbm_cell_dgrad_output_det(const float* M, int B, int H, int W, int C, int stride, float* gx, int parity_class, int ld, int c_off,
+                              float* bias_grad, void* workspace, int64_t workspace_bytes, void* stream);
 /* FORWARD of the pattern pixels with the same 25 products per cell (the correlation form, F(3x3,3x3)): nbm_cell_input of the
  * input, M_xi = Vx_xi U_xi^T (U = E w E^T as [25][N][C]), then blk = E^T M E + bias into the 3x3 pattern block of every cell of
  * y [B][H][W][N] (other pixels are not written). */
@@ -433,6 +452,11 @@ int nbm_stem7x7(const float* img, int B, int H, int W, const float* weff, const 
  * the image, so that V[n][r][s] = S[n] - Cb[n][7 r + s] counts the init_conv bias only inside conv1's zero padding.  The
  * caller forms dW1 = a U + b V, da = sum W1 U, db = sum W1 V (backbone.py:104-113,131). */
 int nbm_stem7x7_wgrad(const float* img, const float* g, int B, int H, int W, float* D, float* Cb, void* stream);
+/* its deterministic twin (see the twins under nbm_conv_wgrad_workspace): every workgroup of both kernels stores its accumulators into
+ * its own slot of `workspace` (16-byte aligned, >= nbm_stem7x7_wgrad_workspace bytes, host-only query), added in slot order. */
+int nbm_stem7x7_wgrad_workspace(int B, int H, int W, int64_t* bytes);
+int nbm_stem7x7_wgrad_det(const float* img, const float* g, int B, int H, int W, float* D, float* Cb, void* workspace,
+                          int64_t workspace_bytes, void* stream);
 
 /* 3x3 / stride 2 / pad 1 max pooling -- torchvision ResNet `maxpool` (backbone.py:131).  idx (may be NULL; training):
  * one byte per output element = r*3+s of the first maximum in scan order, consumed by nbm_maxpool3x3s2_bwd. */
@@ -709,6 +733,12 @@ typedef struct nbm_bwd_desc {
   const unsigned* mask_bits;/* dgrad (round 5): the ReLU mask as BITS instead of `mask` -- [M][Cin / 32] words, bit c % 32 of word
                             m * (Cin / 32) + c / 32 (bit order of nbm_gemm_desc.bits_out) set where the producer's output was > 0 -- or NULL.
                             Cin % 32 == 0, one group; takes precedence over `mask`.                                          */
+  float* workspace;      /* wgrad: NULL = the default kernels (fp32 atomics).  Else the DETERMINISTIC twin: every pixel split stores
+                            its scaled dW tile and its bias partial into its own slice of `workspace`, and an ordered reduction adds
+                            the slices in split order into `out` / `bias_grad` (still +=).  No atomic; the workspace needs no zeroing.
+                            16-byte aligned; size and stride from nbm_conv_wgrad_workspace.                                          */
+  int64_t ws_split_stride;/* wgrad: floats between the slices of consecutive splits (>= what nbm_conv_wgrad_workspace reports, % 4 == 0) */
+  int64_t workspace_bytes;/* wgrad: bytes behind `workspace`; splits * ws_split_stride * 4 must fit                                   */
 } nbm_bwd_desc;
 
 /* dX[b][iy][ix][c] = alpha * sum_{r,s,n} g[b][(iy+pad-r)/stride][(ix+pad-s)/stride][n] * a_scale[n] * W[n][r][s][c]
@@ -719,6 +749,35 @@ int nbm_conv_dgrad(const nbm_bwd_desc* d, void* stream);
 /* dW[n][(r,s,c)] += alpha * row_scale[n] * sum_m g[m][n] * x[pix(m)+(r,s)][c]; dW must be zeroed by the caller.
  * Also the plain C[N][Cin] += A[M][N]^T * B[M][Cin] ("TN") GEMM. */
 int nbm_conv_wgrad(const nbm_bwd_desc* d, void* stream);
+/* Workspace of nbm_conv_wgrad's deterministic twin for this descriptor (its `workspace` fields are ignored): *bytes = splits x slice,
+ * with `splits` of the twin's plan (nbm_gemm_plan of the descriptor with `workspace` set; at most 1 GiB, a plan beyond it gets fewer
+ * splits; ONE slice beyond it: NBM_EUNSUPPORTED) and slice = groups * N * ceil4(kh * kw * Cin) floats (+ ceil4(groups * N) where bias_grad
+ * is set) = *split_stride (may be NULL) -- the rows at their own pitch, not at out_ld.  *bytes = 0: one split and no bias gradient -- the default kernel adds one value per element, nothing to order.  Host only,
+ * launches nothing; returns what nbm_conv_wgrad would return for an invalid descriptor. */
+int nbm_conv_wgrad_workspace(const nbm_bwd_desc* d, int64_t* bytes, int64_t* split_stride);
+
+/* ---- deterministic twins of the reductions that sum with floating-point atomics (train.py --deterministic; no reference counterpart).
+ * Each twin's workgroups STORE partial sums into slots of `workspace` (16-byte aligned, >= nbm_det_workspace bytes, never zeroed, its
+ * previous contents never read) and an ordered reduction adds the slots in ascending order: the same bits on every launch, whatever the
+ * placement of the workgroups.  Arguments before `workspace` are those of the default entry point. */
+enum { NBM_DET_COLSUM = 0, NBM_DET_SQNORM = 1, NBM_DET_BN = 2, NBM_DET_WEIGHTED_SUM = 3, NBM_DET_DWCONV = 4 };
+/* workspace bytes of twin `op` -- COLSUM / BN: rows = M, cols = N / C; SQNORM / WEIGHTED_SUM: rows = n, cols = 1; DWCONV: rows =
+ * B * Ho * Wo, cols = Cin * mult.  Host only. */
+int nbm_det_workspace(int op, int64_t rows, int cols, int64_t* bytes);
+/* the ordered reduction itself: out[i] (+)= sum_{s < slots} part[s * n + i] in ascending s; part float or double (part_is_double) */
+int nbm_ordered_sum(const void* part, int part_is_double, int slots, int64_t n, float* out, int accumulate, void* stream);
+int nbm_colsum_det(const float* g, int64_t M, int N, int ld, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+int nbm_weighted_sum_bwd_det(const float* x0, const float* x1, const float* x2, const float* weights, const float* g, float* gx0,
+                             float* gx1, float* gx2, float* gw, int64_t n, void* workspace, int64_t workspace_bytes, void* stream);
+int nbm_dwconv3x3_bwd_det(const float* x, const float* g, const float* w, int B, int H, int W, int Cin, int mult, int stride, float* gx,
+                          float* gw, float* gb, int Ho, int Wo, void* workspace, int64_t workspace_bytes, void* stream);
+int nbm_bn_train_fwd_det(const float* x, int64_t M, int C, const float* w, const float* b, float eps, float momentum, float* run_mean,
+                         float* run_var, double* stats_ws, float* mean, float* invstd, float* y, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int nbm_bn_train_bwd_det(const float* g, const float* x, int64_t M, int C, const float* mean, const float* invstd, const float* w,
+                         double* red_ws, float* gx, float* gw, float* gb, void* workspace, int64_t workspace_bytes, void* stream);
+/* *out += sum g^2, partials and sum in double */
+int nbm_sqnorm_accum_det(const float* g, int64_t n, double* out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The launch plan of the three GEMM entry points: which kernel instantiation a descriptor runs on, with what grid, and the tiling values
  * the launch derives beyond the descriptor (csrc/igemm_plan.h; no counterpart in the reference, whose convolutions are dispatched inside
@@ -890,6 +949,12 @@ int nbm_bn_act_train_bwd(const float* gy, const float* y, const float* z, int64_
 int nbm_roi_pool_hw_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
                         const float* rois, const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
                         void* stream);
+/* Deterministic twin, gather form: a workgroup owns a 16 x 16 pixel tile of one level and image, walks the image's RoIs in index order and
+ * adds each RoI's shares for the pixels inside its window (the same window function), one read-modify-write per touched element and no
+ * atomic.  Pixels outside every window are not written (the footprint of nbm_zero_roi_windows holds).  Work grows linearly with n_roi. */
+int nbm_roi_pool_hw_bwd_det(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
+                            const float* rois, const int* level, int B, int n_roi, int pool_h, int pool_w, const float* gpool,
+                            void* stream);
 /* nbm_roi_pool_hw_bwd with pool_h = pool_w = 2 (gpool [B*n_roi][2][2][C]): same kernel, same argument checks */
 int nbm_roi_pool_bwd(float* const* gfmap_host, const int* fh_host, const int* fw_host, int n_levels, int C,
                      const float* rois, const int* level, int B, int n_roi, const float* gpool, void* stream);
