@@ -94,6 +94,12 @@ class GemmPlan(C.Structure):
                 ('plain', C.c_int), ('b_generic', C.c_int), ('narrow_m', C.c_int), ('halves', C.c_int)]
 
 
+class MhaPlan(C.Structure):
+    """struct nbm_mha_plan_t (include/nbm_hip.h)."""
+    _fields_ = [('rc', C.c_int), ('family', C.c_int), ('lds_bytes', C.c_int), ('lds_bytes_bwd', C.c_int), ('rows', C.c_int),
+                ('row_blocks', C.c_int), ('workspace_bytes', C.c_int64)]
+
+
 _P, _I, _L, _F, _U64, _U32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64, C.c_uint32
 
 # name -> argtypes (restype is int unless noted); must list every symbol of include/nbm_hip.h
@@ -152,6 +158,7 @@ SIGNATURES = {
     'nbm_conv_dgrad': [C.POINTER(BwdDesc), _P],
     'nbm_conv_wgrad': [C.POINTER(BwdDesc), _P],
     'nbm_gemm_plan': [_I, _P, C.POINTER(GemmPlan)],
+    'nbm_mha_plan': [_I, _I, _I, _I, C.POINTER(MhaPlan)],
     'nbm_relu_bwd': [_P, _P, _P, _L, _P],
     'nbm_silu_bwd': [_P, _P, _P, _L, _P],
     'nbm_axpby': [_P, _P, _P, _F, _F, _L, _L, _P],

@@ -314,7 +314,9 @@ class Transformer_RCNN(nn.Module):
     """reference layers.py:589-651 (`--tf_rcnn`).  Default flavour: post-norm ReLU encoder fed
     rois_embed + pos_embed with batch_first=False, i.e. the reference attends ACROSS THE IMAGES OF THE BATCH for each RoI
     slot (sequence axis = bs, <= 128 here); `tf_pe_qk`: DETR flavour, attention across the RoIs of one image with
-    q = k = src + pos and LeakyReLU.
+    q = k = src + pos and LeakyReLU (sequence axis = RoI slots, <= 1024: `--post_nms_topN_eval` / `--rcnn_batch_size` beyond
+    that are refused here, at construction -- both budgets whatever the model is then used for, so a checkpoint whose `args` hold
+    a training budget above 1024 is refused by `load_model` too, although its evaluation budget alone would run).
     `--dropout p` (0 <= p < 1): in training mode both flavours drop at four sites per encoder layer -- the attention probabilities,
     dropout1 behind out_proj, the feed-forward's dropout behind its activation, dropout2 behind linear2 (reference
     self_attention.py:113-135; nn.TransformerEncoderLayer) -- with masks that are a function of (seed, call, 4 * layer + site,
@@ -336,6 +338,11 @@ class Transformer_RCNN(nn.Module):
         self.nhead = config.tf_nhead
         if self.nhead < 1 or E % self.nhead or E // self.nhead > 512:    # csrc/mha.hip: MHA_HDWIDE
             raise NotImplementedError('Transformer_RCNN: tf_nhead must divide tf_model_dim and the head dim be <= 512')
+        if self.tf_pe_qk:           # the RoI slots of an image are the sequence: evaluation and training budgets (csrc/mha.hip: MHA_SLONG)
+            for flag in ('post_nms_topN_eval', 'rcnn_batch_size'):
+                if int(getattr(config, flag)) > ops.MHA_SLONG:
+                    raise NotImplementedError(f'Transformer_RCNN (--tf_rcnn --tf_pe_qk) attends across the RoI slots of an image and takes '
+                                              f'at most {ops.MHA_SLONG} of them: --{flag} {getattr(config, flag)} is beyond that limit')
         self.pos_embedding = nn.Sequential(nn.Linear(in_dim, E), nn.LeakyReLU())
         self.rois_embedding = nn.Sequential(nn.Linear(in_dim, E), nn.LeakyReLU())
         self.encoder = _Encoder(E, self.nhead, config.tf_dim_feedforward, config.tf_num_encoder_layers)

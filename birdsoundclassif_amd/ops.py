@@ -990,9 +990,11 @@ def layernorm(x2d, w, b, eps=1e-5):
 
 
 def mha_small(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid=None):
-    """q, k, v: 2-D row views [S*N, >= E] (column slices of a fused projection are fine) -> out [S*N, E].  S <= MHA_SMAX; any
-    head dim E // nhead <= 512 (csrc/mha.hip: one lane per column up to 64, chunked wide kernels above); the same holds for
-    `mha_segments`, `mha_small_drop` and the two backwards."""
+    """q, k, v: 2-D row views [S*N, >= E] (column slices of a fused projection are fine) -> out [S*N, E].  S <= MHA_SLONG; any
+    head dim E // nhead <= 512.  csrc/mha.hip: up to MHA_SMAX tokens one lane per column for head dims up to 64 and the chunked
+    wide kernels above; MHA_SMAX < S <= MHA_SLONG the long kernels (K and V through LDS in blocks of 128 keys, plain softmax
+    over the whole row) -- the choice follows S, never *n_valid, and `mha_plan` reports it.  The same holds for `mha_small_drop`,
+    the two backwards and `mha_segments` in MHA_ACROSS_ROIS."""
     E = q.shape[1]
     hd = E // nhead
     for t in (q, k, v):
@@ -1003,15 +1005,29 @@ def mha_small(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid=None):
     return out
 
 
-MHA_SMAX = 128                  # csrc/mha.hip: longest sequence of nbm_mha_small / nbm_mha_segments / nbm_mha_segments_wide
+MHA_SMAX = 128                  # csrc/mha.hip: longest sequence of the short kernels, and of a segment in MHA_ACROSS_IMAGES
+MHA_SLONG = 1024                # csrc/mha.hip: longest sequence of nbm_mha_small* and of nbm_mha_segments_wide in MHA_ACROSS_ROIS
 MHA_ACROSS_ROIS, MHA_ACROSS_IMAGES = 0, 1
+
+MhaPlan = collections.namedtuple('MhaPlan', 'family lds_bytes lds_bytes_bwd rows row_blocks workspace_bytes')
+
+
+def mha_plan(S, hd, N=1, nhead=1):
+    """What `mha_small`, `mha_small_drop` and their backwards run on for sequences of S tokens and head dim hd (nbm_mha_plan,
+    include/nbm_hip.h): family 'narrow' / 'wide' / 'long', the static LDS bytes of the forward and of the backward's pass 1, the
+    query rows per workgroup, the workgroups per (batch entry, head) and the bytes of the backward's workspace for N entries of
+    nhead heads.  Nothing is launched; works without a GPU.  A geometry the entry points refuse raises NbmHipError (NBM_EINVAL)."""
+    p = _lib.MhaPlan()
+    check(lib().nbm_mha_plan(int(S), int(hd), int(N), int(nhead), C.byref(p)), 'nbm_mha_plan')
+    return MhaPlan(('narrow', 'wide', 'long')[p.family], p.lds_bytes, p.lds_bytes_bwd, p.rows, p.row_blocks, p.workspace_bytes)
 
 
 def mha_segments(q, k, v, R, nhead, mode, segments, n_roi, max_count=None):
     """`mha_small` for a batch that is several model calls (evaluation only): q, k, v 2-D row views [B*R, >= E], token (b, r) =
     row b*R + r; `segments` the int32 [2, B] device table (`segment_table`), `n_roi` int32 [B] device counts (equal within a
-    segment) -> out [B*R, E].  MHA_ACROSS_ROIS: attention over the RoIs r < n_roi[b] of each image; MHA_ACROSS_IMAGES: for
-    every slot r < n_roi of a segment, over the segment's images.  Every row is written by the kernel -- zeros where there
+    segment) -> out [B*R, E].  MHA_ACROSS_ROIS: attention over the RoIs r < n_roi[b] of each image, R <= MHA_SLONG (above
+    MHA_SMAX slots through the long kernels, as `mha_small` with S = R); MHA_ACROSS_IMAGES: for every slot r < n_roi of a segment,
+    over the segment's images, at most MHA_SMAX of them, any R.  Every row is written by the kernel -- zeros where there
     is no token -- so `out` is not pre-filled; valid rows equal `mha_small` on the segment alone bit for bit.
     `max_count`: largest segment of the table (default: the most a table of B images can hold, capped at MHA_SMAX -- the
     rows of a longer segment come out zero)."""
@@ -1107,7 +1123,8 @@ def mha_small_drop(q, k, v, S, N, nhead, seq_stride, batch_stride, n_valid, p, s
 
 
 def mha_small_drop_bwd(q, k, v, go, S, N, nhead, seq_stride, batch_stride, n_valid, p, seed, call, site_id):
-    """Gradients of `mha_small_drop` wrt q, k, v (the mask is evaluated again) -> contiguous [S*N, E] each."""
+    """Gradients of `mha_small_drop` wrt q, k, v (the mask is evaluated again) -> contiguous [S*N, E] each.  S <= MHA_SLONG;
+    workspace as `mha_small_bwd`."""
     E = q.shape[1]
     hd = E // nhead
     gq, gk, gv = (torch.zeros((q.shape[0], E), device=q.device, dtype=torch.float32) for _ in range(3))
@@ -1777,7 +1794,9 @@ def layernorm_bwd(x2d, w, g2d, eps=1e-5):
 
 
 def mha_small_bwd(q, k, v, go, S, N, nhead, seq_stride, batch_stride, n_valid=None):
-    """Gradients of `mha_small` wrt q, k, v (2-D row views, any row pitch) -> contiguous [S*N, E] each."""
+    """Gradients of `mha_small` wrt q, k, v (2-D row views, any row pitch) -> contiguous [S*N, E] each.  S <= MHA_SLONG.  The
+    workspace is 8 * N * nhead * S * S bytes (`mha_plan(...).workspace_bytes`), allocated here for the call: 8 MiB per (entry,
+    head) at S = 1024."""
     E = q.shape[1]
     hd = E // nhead
     gq, gk, gv = (torch.zeros((q.shape[0], E), device=q.device, dtype=torch.float32) for _ in range(3))

@@ -511,13 +511,15 @@ int nbm_silu(const float* x, float* y, int64_t n, void* stream);
  * Transformer_RCNN head (reference layers.py:589-651, self_attention.py:110-131). */
 int nbm_layernorm(const float* x, int64_t rows, int E, const float* w, const float* b, float eps, float* y, void* stream);
 
-/* out = softmax(scale * Q K^T) V per (batch entry, head) for short sequences (S <= 128, hd <= 512): token (s, n) is row
+/* out = softmax(scale * Q K^T) V per (batch entry, head) for sequences of S <= 1024 tokens, hd <= 512: token (s, n) is row
  * s*seq_stride + n*batch_stride of q/k/v/out (row pitches *_ld floats, head h at columns [h*hd, (h+1)*hd)); keys with
  * s >= *n_valid (device counter, may be NULL) are masked -- nn.MultiheadAttention inside the Transformer_RCNN encoder
  * (reference layers.py:613-621,645-646; self_attention.py:110-126).  hd <= 64: one lane per output column, K and V of an
  * (entry, head) whole in LDS; 64 < hd <= 512: the head dimension passes through LDS in 64-column chunks (csrc/mha.hip, "wide
- * heads"); hd > 512 is NBM_EINVAL.  The same split and limit hold for the three entry points below that share this token layout and for
- * nbm_mha_segments_wide. */
+ * heads"); hd > 512 is NBM_EINVAL.  128 < S <= 1024, any hd: the "long" kernels -- K and V pass through LDS in blocks of 128 keys,
+ * the score rows of 8 queries wait in LDS, the softmax is the plain one over the whole row; the choice follows the launch's S,
+ * never *n_valid.  S > 1024 is NBM_EINVAL with nothing launched.  The same split and limits hold for the three entry points below
+ * that share this token layout, and for nbm_mha_segments_wide in ACROSS_ROIS (nbm_mha_plan reports the choice). */
 int nbm_mha_small(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
                   int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                   float scale, void* stream);
@@ -538,7 +540,9 @@ int nbm_mha_segments(const float* q, const float* k, const float* v, int q_ld, i
                      int B, int R, int nhead, int hd, int mode, const int32_t* segments, const int32_t* n_roi, int max_count,
                      float scale, void* stream);
 /* nbm_mha_segments for every head dim nbm_mha_small takes, 1 <= hd <= 512: the same arguments, checks and results; hd <= 64 is
- * the launch nbm_mha_segments makes, above it the wide segments kernel (csrc/mha.hip).  hd > 512: NBM_EINVAL. */
+ * the launch nbm_mha_segments makes, above it the wide segments kernel (csrc/mha.hip).  hd > 512: NBM_EINVAL.
+ * ACROSS_ROIS also takes 128 < R <= 1024 slots, through the long kernels of nbm_mha_small (a valid row holds the bits
+ * nbm_mha_small gives with S = R); R > 1024: NBM_EINVAL.  ACROSS_IMAGES takes any R and keeps max_count <= 128. */
 int nbm_mha_segments_wide(const float* q, const float* k, const float* v, int q_ld, int k_ld, int v_ld, float* out, int out_ld,
                           int B, int R, int nhead, int hd, int mode, const int32_t* segments, const int32_t* n_roi,
                           int max_count, float scale, void* stream);
@@ -803,6 +807,24 @@ typedef struct nbm_gemm_plan_t {
 } nbm_gemm_plan_t;
 int nbm_gemm_plan(int kind, const void* desc, nbm_gemm_plan_t* out);
 
+/* What a launch of nbm_mha_small, nbm_mha_small_drop or their backwards with this S, hd, N and nhead runs on (csrc/mha.hip), in the spirit
+ * of nbm_gemm_plan: host only, launches nothing, touches no HIP API.  family: narrow (S <= 128, hd <= 64), wide (S <= 128, 64 < hd <= 512)
+ * or long (128 < S <= 1024, hd <= 512); nbm_mha_segments_wide in ACROSS_ROIS takes the family of (R, hd).  Returns (and stores in rc)
+ * NBM_OK, or the NBM_EINVAL the entry points return for that geometry, with the other fields zero. */
+#define NBM_MHA_NARROW 0
+#define NBM_MHA_WIDE 1
+#define NBM_MHA_LONG 2
+typedef struct nbm_mha_plan_t {
+  int rc;
+  int family;
+  int lds_bytes;            /* static LDS of the forward kernel's workgroup ...                                                  */
+  int lds_bytes_bwd;        /* ... and of the backward's pass 1 (pass 2 uses none)                                               */
+  int rows;                 /* query rows per workgroup (narrow: the whole sequence)                                             */
+  int row_blocks;           /* workgroups per (batch entry, head)                                                                */
+  int64_t workspace_bytes;  /* the backward's workspace: 2 * S * S floats per (batch entry, head)                                */
+} nbm_mha_plan_t;
+int nbm_mha_plan(int S, int hd, int N, int nhead, nbm_mha_plan_t* out);
+
 int nbm_relu_bwd(const float* gy, const float* y, float* out, int64_t n, void* stream);
 int nbm_silu_bwd(const float* gy, const float* x, float* out, int64_t n, void* stream);
 /* out[i] = alpha*a[i] + beta*b[i % b_period] (b may be NULL; b_period 0: b has n elements): gradient accumulation, the
@@ -844,7 +866,7 @@ int nbm_leaky_relu_bwd(const float* gy, const float* y, float* out, float slope,
 int nbm_layernorm_bwd(const float* x, const float* w, const float* g, int64_t rows, int E, float eps, float* gx, float* gw,
                       float* gb, void* stream);
 /* backward of nbm_mha_small: gq/gk/gv get every VALID token row written (pre-zero them when *n_valid < S);
- * workspace: 2*S*S floats per (batch entry, head), whatever hd (<= 512) */
+ * workspace: 2*S*S floats per (batch entry, head), whatever hd (<= 512) and S (<= 1024; 8 MiB per (entry, head) there) */
 int nbm_mha_small_bwd(const float* q, const float* k, const float* v, const float* go, int q_ld, int k_ld, int v_ld,
                       int go_ld, float* gq, float* gk, float* gv, int gq_ld, int gk_ld, int gv_ld, float* workspace, int S,
                       int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
@@ -866,7 +888,7 @@ int nbm_mha_small_bwd(const float* q, const float* k, const float* v, const floa
 int nbm_dropout(const float* x, const float* residual, float* y, int64_t n, uint32_t threshold, float scale, uint64_t seed,
                 uint32_t call, uint32_t site_id, void* stream);
 /* nbm_mha_small with dropout on the softmax probabilities: A[r][j] = keep ? (e_j / sum) * drop_scale : 0, out = A V.  Token layout,
- * *n_valid handling, limits (S <= 128, hd <= 512) and argument checks are nbm_mha_small's.  The mask element of (batch entry n,
+ * *n_valid handling, limits (S <= 1024, hd <= 512) and argument checks are nbm_mha_small's.  The mask element of (batch entry n,
  * head h, query r, key j) is ((n * nhead + h) * S + r) * S + j -- a dense [N][nhead][S][S] tensor, S the launch's S whatever
  * *n_valid holds.
  * Replaces: nn.MultiheadAttention(dropout=p) in training mode, self_attention.py:113,131 / layers.py:619-621. */
@@ -874,7 +896,7 @@ int nbm_mha_small_drop(const float* q, const float* k, const float* v, int q_ld,
                        int S, int N, int nhead, int hd, int64_t seq_stride, int64_t batch_stride, const int32_t* n_valid,
                        float scale, uint32_t threshold, float drop_scale, uint64_t seed, uint32_t call, uint32_t site_id,
                        void* stream);
-/* backward of nbm_mha_small_drop (arguments, workspace and hd <= 512 of nbm_mha_small_bwd): dA = dO V^T, dP = keep ? dA * drop_scale : 0,
+/* backward of nbm_mha_small_drop (arguments, workspace, S <= 1024 and hd <= 512 of nbm_mha_small_bwd): dA = dO V^T, dP = keep ? dA * drop_scale : 0,
  * dS = P (dP - sum_j P dP), dQ = scale dS K, dK = scale dS^T Q, dV = A^T dO.
  * Replaces: autograd through nn.MultiheadAttention(dropout=p), train.py:212. */
 int nbm_mha_small_drop_bwd(const float* q, const float* k, const float* v, const float* go, int q_ld, int k_ld, int v_ld,
